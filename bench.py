@@ -304,6 +304,13 @@ def run_gpu(args, rank, world, device):
             reuse = prepare_batch_on_gpu(dict(batches[0]), net, dataset.voxel_cfg)
         torch.cuda.synchronize()
 
+    # what the caller of the last timed step receives (references only, read after the clock has stopped): --dump-outputs
+    last_it, last = args.warmup + args.steps - 1, {}
+
+    def keep(it, loss, tb):
+        if it == last_it:
+            last.update({"loss": loss, **{f"tb.{k}": v for k, v in tb.items() if torch.is_tensor(v)}})
+
     def step(it):
         if throttle:
             if len(step_done) >= throttle:
@@ -313,6 +320,7 @@ def run_gpu(args, rank, world, device):
             optimizer.zero_grad()
             ret, tb, _ = model(dict(reuse))
             loss = ret["loss"].mean()
+            keep(it, loss, tb)
             loss.backward()
             clip_and_step(optimizer, params, clip)
             net.update_global_step()
@@ -334,6 +342,8 @@ def run_gpu(args, rank, world, device):
                 for m in (net.vfe, net.backbone_3d, net.map_to_bev_module):
                     batch = m(batch)
                 out = batch["spatial_features"].sum()
+                if it == last_it:
+                    last["spatial_features"] = batch["spatial_features"]
                 if prefetch is not None:
                     prefetch.kick()          # (same thread: the next batch's voxelisation + rulebooks on the side stream, under this forward)
             return out
@@ -343,7 +353,7 @@ def run_gpu(args, rank, world, device):
         optimizer.zero_grad()
         if pair:
             adv, org = prefetch.next() if prefetch is not None else batches[it % len(batches)]
-            loss = cl_fn(model, dict(adv), dict(org), world > 1).loss
+            loss, tb, _ = cl_fn(model, dict(adv), dict(org), world > 1)
         else:
             if prefetch is not None:
                 batch = prefetch.next()
@@ -360,6 +370,7 @@ def run_gpu(args, rank, world, device):
                 t_ph = time.perf_counter()
             ret, tb, _ = model(batch)
             loss = ret["loss"].mean()
+        keep(it, loss, tb)
         if ph is not None:
             ph["forward"] += time.perf_counter() - t_ph
             t_ph = time.perf_counter()
@@ -448,6 +459,13 @@ def run_gpu(args, rank, world, device):
         print("[losses] " + " ".join(f"{float(v):.7g}" for v in torch.stack([v.float().reshape(()) for v in loss_log]).tolist()), file=sys.stderr)
     assert np.isfinite(final_loss), "training diverged"
     step_ms = [marks[k].elapsed_time(marks[k + 1]) for k in range(args.steps)]
+    dumped = None
+    if args.dump_outputs and rank == 0:       # before any untimed step below changes the model
+        arrays = dict(last)
+        if not fwd_only:                     # a train step hands its caller the updated model and leaves the gradients on it
+            arrays.update({f"state.{k}": v for k, v in net.state_dict().items()})
+            arrays.update({f"grad.{k}": p.grad for k, p in net.named_parameters() if p.grad is not None})
+        dumped = dump_outputs(arrays, args.dump_outputs)
     op_rows = None
     if args.layers and rank == 0:
         from toda_amd.tools.op_table import OpTable
@@ -489,6 +507,7 @@ def run_gpu(args, rank, world, device):
                            backend="gloo, ranks SHARING one GPU (TODA_BENCH_SHARE_GPU rehearsal)" if os.environ.get("TODA_BENCH_SHARE_GPU") == "1" else "rccl")
     return {"host_input": host_input, "step_sizes": step_sizes, "elapsed": elapsed, "per_gpu": per_gpu, "desc": desc, "loss": final_loss, "timer": timer, "cfg": cfg,
             "dataset": dataset, "model": net, "step_ms": step_ms, "comm": comm, "op_rows": op_rows, "issue_s": t_issued, "cpu_s": cpu_busy,
+            "dumped": dumped,
             "host_step_ms": [t * 1e3 for t in host_step_s],
             "device_allocs": [alloc_marks[k + 1][0] - alloc_marks[k][0] for k in range(args.steps)],
             "alloc_retries": [alloc_marks[k + 1][1] - alloc_marks[k][1] for k in range(args.steps)]}
@@ -503,6 +522,38 @@ PMC_FILES = {("native", 64, 64, 27): ("r05_pmc_gather_gemm_64x64.json", "gather_
              ("native", 32, 32, 27): ("r05_pmc_gather_gemm_32x32.json", "gather_gemm_lds_kernel<2, 2, 2", 2, 1024),
              ("split", 32, 32, 27): ("r05_pmc_split_32x32.json", "gg_split_kernel<1, 1, 2, 2", 2, 1024)}
 PMC_SOURCES = ("toda_amd/csrc/spconv.hip", "toda_amd/csrc/spconv_split.cuh", "toda_amd/csrc/split_common.cuh")
+
+
+DUMP_BYTES = 64_000_000        # --dump-outputs: bound on the bytes written, .npy headers included
+DUMP_WHOLE_BYTES = 1 << 20     # arrays up to this size are always written whole
+
+
+def dump_outputs(arrays, out_dir, budget=DUMP_BYTES):
+    """Write {name: tensor} as out_dir/<name>.npy: float64 and integer tensors as float64, every other one as float32.  When the
+    whole set would exceed `budget` bytes, every array larger than DUMP_WHOLE_BYTES is replaced by a 1-D sample of its flattened
+    elements (ascending indices drawn by a generator of fixed seed, so two runs on the same shapes sample the same elements),
+    the larger arrays sharing what the small ones leave of the budget.  Returns {name: (shape, elements written)}."""
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        wide = t.dtype == torch.float64 or not t.is_floating_point()
+        host[name] = t.to(torch.float64 if wide else torch.float32).cpu().numpy()
+    header = 128                                           # bytes of an .npy header of these shapes
+    small = sum(a.nbytes + header for a in host.values() if a.nbytes <= DUMP_WHOLE_BYTES)
+    large = sum(a.nbytes + header for a in host.values() if a.nbytes > DUMP_WHOLE_BYTES)
+    if small > budget:
+        raise ValueError(f"--dump-outputs: {small} bytes of small arrays exceed the {budget}-byte budget")
+    scale = min(1.0, (budget - small) / large) if large else 1.0
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, a in host.items():
+        shape = a.shape
+        if scale < 1.0 and a.nbytes > DUMP_WHOLE_BYTES:
+            k = max(1, int((a.nbytes + header) * scale - header) // a.itemsize)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = (shape, a.size)
+    return written
 
 
 def _sha256(path):
@@ -820,7 +871,13 @@ def main(argv=None):
                     help="after the timed region run 3 more steps with every hand-written kernel bracketed by HIP events and print the "
                          "per-kernel roofline table (gather-GEMM, wgrad, Winograd conv, voxelise, rulebooks, BN rows, .dense()) to stderr")
     ap.add_argument("--layers-out", default=None, help="also write that table as JSON to this path")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float32 / float64, at most 64 MB; "
+                         "arrays over 1 MiB become a fixed seeded sample of their elements when the whole set would not fit): the loss, "
+                         "the loss terms, the updated parameters and buffers and the gradients of a train step; the dense BEV map of c2")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:      # plain `python bench.py --gpus N`: become the launcher
         raise SystemExit(launch_ranks(args, argv))
@@ -915,6 +972,9 @@ def main(argv=None):
                                            "voxels_min_max": [int(vx.min()), int(vx.max())]}
         if res.get("comm"):
             line["comm"] = res["comm"]
+        if res["dumped"] is not None:
+            line["dump_outputs"] = {"dir": args.dump_outputs, "arrays": len(res["dumped"]),
+                                    "sampled": sorted(k for k, (shape, n) in res["dumped"].items() if n < int(np.prod(shape)))}
         if world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(res["cfg"], args.workload)
         print(json.dumps(line), flush=True)

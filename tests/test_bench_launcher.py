@@ -7,8 +7,15 @@ import subprocess
 import sys
 
 import pytest
+import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# Every process of a dry run - the launcher and each rank - initialises the HIP runtime (torch.distributed and the autograd
+# engine count the devices), and on a machine with a GPU that opens the GPU.  A shared GPU machine allows at most 6 processes
+# per GPU to have it open, so the eight-rank runs (launcher + 8 ranks + this process) run where no GPU is visible.
+host_only_world_8 = pytest.mark.skipif(torch.cuda.is_available(), reason="8 ranks + launcher + pytest would each open the GPU "
+                                                                          "(a shared GPU machine allows 6 per GPU)")
 
 
 def _run(extra_env, *argv):
@@ -62,6 +69,7 @@ def test_two_rank_rehearsal_of_the_n_gpu_bench_path(reducer):
     assert comm["ms_per_step_without_allreduce"] > 0 and line["ms_per_step"] > 0 and line["value"] > 0
 
 
+@host_only_world_8
 @pytest.mark.timeout(1500)
 @pytest.mark.parametrize("reducer", ["own", "torch"])
 def test_world_8_rehearsal_places_every_rank_and_all_eight_answer(reducer):
@@ -85,8 +93,38 @@ def test_world_8_rehearsal_places_every_rank_and_all_eight_answer(reducer):
         assert len(set(flat)) == len(flat), f"ranks share CPUs: {cpus}"
 
 
+@host_only_world_8
 @pytest.mark.timeout(900)
 def test_missing_rank_line_is_a_failure_at_world_8():
     """A rank that dies takes the launcher's exit status with it at N = 8 too (no JSON line is accepted from a partial job)."""
     p = _run({"TODA_BENCH_DRYRUN_FAIL_RANK": "5"}, "--gpus", "8")
     assert p.returncode != 0
+
+
+def test_dump_outputs_keeps_small_arrays_and_samples_large_ones_within_the_budget(tmp_path):
+    """--dump-outputs: dtypes (float64 / integers -> float64, the rest -> float32), whole small arrays, and a seeded sample of the
+    large ones that fits the byte budget and picks the same elements on every call."""
+    import numpy as np
+
+    import bench
+
+    g = torch.Generator().manual_seed(0)
+    arrays = {"loss": torch.tensor(2.5), "count": torch.tensor(7), "w64": torch.randn(3, 4, dtype=torch.float64, generator=g),
+              "big_a": torch.randn(600_000, generator=g), "big_b": torch.randn(3, 250_000, dtype=torch.float16, generator=g)}
+    budget = 3_000_000
+    for d in (tmp_path / "one", tmp_path / "two"):
+        written = bench.dump_outputs(arrays, str(d), budget=budget)
+        assert sum(f.stat().st_size for f in d.iterdir()) <= budget
+    one = {f.stem: np.load(f) for f in (tmp_path / "one").iterdir()}
+    two = {f.stem: np.load(f) for f in (tmp_path / "two").iterdir()}
+    assert sorted(one) == sorted(arrays) and all(np.array_equal(one[k], two[k]) for k in one)
+    assert one["loss"].dtype == np.float32 and float(one["loss"]) == 2.5
+    assert one["count"].dtype == np.float64 and float(one["count"]) == 7
+    assert one["w64"].dtype == np.float64 and np.array_equal(one["w64"], arrays["w64"].numpy())
+    for k in ("big_a", "big_b"):
+        full = arrays[k].float().numpy().reshape(-1)
+        got = one[k]
+        assert got.dtype == np.float32 and 0 < got.size < full.size and written[k] == (tuple(arrays[k].shape), got.size)
+        assert np.isin(got, full).all()
+    ok = bench.dump_outputs({"x": torch.randn(600_000, generator=g)}, str(tmp_path / "whole"))
+    assert ok["x"] == ((600_000,), 600_000)
