@@ -99,6 +99,49 @@ int toda_mean_vfe_bwd(const float* grad_out, const float* num_pts, int m, int p,
                       float* grad_voxels, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Dynamic voxelisation (DynPillarVFE / DynMeanVFE): every in-range point is
+ * kept, no caps.  points [n, width] is the collated batch (batch index in
+ * column 0, x y z in columns 1-3); pillar != 0: key (b, x, y), x and y
+ * tested (pcdet/models/backbones_3d/vfe/dynamic_pillar_vfe.py:101-109);
+ * 0: key (b, x, y, z), all axes tested (dynamic_mean_vfe.py:55-64).  A row
+ * whose batch index is outside [0, batch) or NaN is dropped like an
+ * out-of-range point.  Integer atomics only; every result is bit-reproducible.
+ * ---------------------------------------------------------------------- */
+size_t toda_dynvox_workspace_bytes(int n, int batch, const int32_t* grid_host, int pillar);
+/* Pass 1: counts_dev[0] = M (distinct keys), counts_dev[1] = K (kept points).
+ * The workspace carries the bitmap and keep positions on to toda_dynvox_index. */
+int toda_dynvox_count(const float* points, int n, int width, int batch, const float* range_host, const float* vsize_host,
+                      const int32_t* grid_host, int pillar, int32_t* counts_dev, void* ws, size_t ws_bytes, void* stream);
+/* Pass 2, with the M and K of pass 1 (same arguments and workspace).  Replaces the mask + merge key +
+ * torch.unique(return_inverse, return_counts) of dynamic_pillar_vfe.py:101-113 / dynamic_mean_vfe.py:55-66 and the
+ * coordinate split of dynamic_pillar_vfe.py:141-148 / dynamic_mean_vfe.py:68-73:
+ * keep [n] (uint8), rows [K] = original index of each kept point (ascending: reference points[mask]), inv [K] = unq_inv
+ * (rows are numbered in torch.unique's ascending key order), cnt [M] = unq_cnt, coords [M, 4] = (b, z, y, x),
+ * seg_off [M + 1] + seg_pts [K]: the kept rows of voxel v are seg_pts[seg_off[v] .. seg_off[v + 1]), ascending. */
+int toda_dynvox_index(const float* points, int n, int width, int batch, const float* range_host, const float* vsize_host,
+                      const int32_t* grid_host, int pillar, int m, int k, uint8_t* keep, int32_t* rows, int32_t* inv,
+                      int32_t* seg_pts, int32_t* seg_off, int32_t* cnt, int32_t* coords, void* ws, size_t ws_bytes,
+                      void* stream);
+/* torch_scatter.scatter_mean / scatter_sum (dynamic_pillar_vfe.py:115, dynamic_mean_vfe.py:66, and the backward of
+ * x_max[unq_inv]): out[v, c] = sum over the segment, in seg_pts order, of src[row, col0 + c]; row = rowmap[j] when rowmap
+ * is given (points read in place through toda_dynvox_index's rows), else j.  divide != 0: / segment length. */
+int toda_dynvox_seg_sum(const float* src, int ld, int col0, int ncol, const int32_t* rowmap, const int32_t* seg_off,
+                        const int32_t* seg_pts, int m, int divide, float* out, void* stream);
+/* dynamic_pillar_vfe.py:110-129: per kept row [points[:, 1:] (use_abs_xyz) or points[:, 4:], xyz - mean[inv],
+ * xyz - pillar centre, (|xyz|)] written as the rows [K, f] the first Linear reads (no torch.cat).
+ * offset_host = (x_offset, y_offset, z_offset) of dynamic_pillar_vfe.py:75-77; mean [M, 3] from toda_dynvox_seg_sum. */
+int toda_dynvox_pillar_decorate(const float* points, int width, const int32_t* rows, const int32_t* inv,
+                                const int32_t* coords, const float* mean, int k, const float* vsize_host,
+                                const float* offset_host, int use_abs_xyz, int with_dist, float* out, int f, void* stream);
+/* torch_scatter.scatter_max (dynamic_pillar_vfe.py:41): out [M, c] and arg [M, c] (row of the maximum; on a tie the
+ * lowest row).  bwd: gx [k, c] = 0, gx[arg[v, c], c] = gout[v, c] (plain stores: a row belongs to one voxel). */
+int toda_dynvox_seg_max_fwd(const float* x, int c, const int32_t* seg_off, const int32_t* seg_pts, int m, float* out,
+                            int32_t* arg, void* stream);
+int toda_dynvox_seg_max_bwd(const float* gout, const int32_t* arg, int m, int c, int k, float* gx, void* stream);
+/* torch.cat([x, x_max[unq_inv, :]], dim=1) (dynamic_pillar_vfe.py:46): out [k, 2c]. */
+int toda_dynvox_gather_concat(const float* x, const float* xmax, const int32_t* inv, int k, int c, float* out, void* stream);
+
+/* ------------------------------------------------------------------------
  * Grid index: a bitmap + popcount-rank dictionary over the (b, z, y, x)
  * lattice of one sparse level.  rank(coord) is the position of the site in
  * ascending ((b*D+z)*H+y)*W+x order, which is the canonical row order of

@@ -23,6 +23,14 @@ SIGNATURES = {
     "toda_voxelize_hard": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "toda_mean_vfe_fwd": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "toda_mean_vfe_bwd": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "toda_dynvox_workspace_bytes": (_sz, [_i, _i, _vp, _i]),
+    "toda_dynvox_count": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
+    "toda_dynvox_index": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "toda_dynvox_seg_sum": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "toda_dynvox_pillar_decorate": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp]),
+    "toda_dynvox_seg_max_fwd": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "toda_dynvox_seg_max_bwd": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "toda_dynvox_gather_concat": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "toda_gridindex_bytes": (_sz, [_i, _vp]),
     "toda_gridindex_from_coords": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "toda_gridindex_from_conv": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),

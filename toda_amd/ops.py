@@ -203,6 +203,150 @@ def mean_vfe(voxels, num_points):
     return _MeanVFE.apply(voxels, num_points)
 
 
+# ----------------------------------------------------------------------- dynamic voxelisation
+class DynVoxelIndex:
+    """The grouping of DynPillarVFE / DynMeanVFE (toda_dynvox_index): keep [N] bool (the in-range mask), rows [K] (original index
+    of each kept point, ascending), inv [K] (unq_inv), cnt [M] (unq_cnt), coords [M, 4] (b, z, y, x), and the CSR view seg_off
+    [M + 1] / seg_pts [K]: the kept rows of voxel v, ascending.  Voxel rows are in torch.unique order of the reference's x-major
+    merge key."""
+
+    def __init__(self, keep, rows, inv, cnt, coords, seg_off, seg_pts, pillar):
+        self.keep, self.rows, self.inv, self.cnt, self.coords = keep, rows, inv, cnt, coords
+        self.seg_off, self.seg_pts, self.pillar = seg_off, seg_pts, pillar
+
+    @property
+    def M(self):
+        return int(self.coords.shape[0])
+
+    @property
+    def K(self):
+        return int(self.rows.shape[0])
+
+
+def dyn_voxel_index(points, pc_range, voxel_size, batch_size, pillar):
+    """points [sum N, 1 + C] (batch index in column 0) -> DynVoxelIndex.  Two passes and ONE host read (M and K, ops.read_counts)."""
+    lib = L.load()
+    assert points.dtype == torch.float32 and points.dim() == 2 and points.shape[1] >= 4
+    points = points.contiguous()
+    n, width = points.shape
+    dev = points.device
+    grid = L.host_i32(grid_size_xyz(pc_range, voxel_size))
+    rng, vs = L.host_f32(pc_range[:3]), L.host_f32(voxel_size)
+    bsz = int(batch_size)
+    ws_bytes = lib.toda_dynvox_workspace_bytes(n, bsz, L.hptr(grid), int(bool(pillar)))
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    counts = torch.empty((2,), dtype=torch.int32, device=dev)
+    L.check(lib.toda_dynvox_count(L.ptr(points), n, width, bsz, L.hptr(rng), L.hptr(vs), L.hptr(grid), int(bool(pillar)), L.ptr(counts),
+                                  L.ptr(ws), ws_bytes, L.stream()), "toda_dynvox_count")
+    m, k = read_counts(counts)      # the one sync
+    keep = torch.empty((n,), dtype=torch.bool, device=dev)
+    rows = torch.empty((k,), dtype=torch.int32, device=dev)
+    inv = torch.empty((k,), dtype=torch.int32, device=dev)
+    seg_pts = torch.empty((k,), dtype=torch.int32, device=dev)
+    seg_off = torch.empty((m + 1,), dtype=torch.int32, device=dev)
+    cnt = torch.empty((m,), dtype=torch.int32, device=dev)
+    coords = torch.empty((m, 4), dtype=torch.int32, device=dev)
+    rc = lib.toda_dynvox_index(L.ptr(points), n, width, bsz, L.hptr(rng), L.hptr(vs), L.hptr(grid), int(bool(pillar)), m, k,
+                               L.ptr(keep), L.ptr(rows), L.ptr(inv), L.ptr(seg_pts), L.ptr(seg_off), L.ptr(cnt), L.ptr(coords),
+                               L.ptr(ws), ws_bytes, L.stream())
+    L.check(rc, "toda_dynvox_index")
+    return DynVoxelIndex(keep, rows, inv, cnt, coords, seg_off, seg_pts, bool(pillar))
+
+
+def dyn_seg_sum(src, index, col0=0, ncol=None, rowmap=None, mean=False):
+    """[M, ncol]: per voxel the sum (mean=True: the mean) of src[row, col0:col0 + ncol] over its rows, in seg_pts order.  rowmap:
+    the segment's entries are rows of `rowmap` (index.rows: read the collated points in place)."""
+    src = src.contiguous()
+    ld = src.shape[1]
+    ncol = ld - col0 if ncol is None else ncol
+    out = torch.empty((index.M, ncol), dtype=torch.float32, device=src.device)
+    rc = L.load().toda_dynvox_seg_sum(L.ptr(src), ld, int(col0), int(ncol), L.ptr(rowmap), L.ptr(index.seg_off), L.ptr(index.seg_pts),
+                                      index.M, int(bool(mean)), L.ptr(out), L.stream())
+    L.check(rc, "toda_dynvox_seg_sum")
+    return out
+
+
+def dyn_points_mean(points, index, col0=1, ncol=None):
+    """scatter_mean of the kept points' columns col0 .. (DynMeanVFE: all features; DynPillarVFE: xyz)."""
+    return dyn_seg_sum(points, index, col0, ncol, rowmap=index.rows, mean=True)
+
+
+def dyn_pillar_decorate(points, index, mean_xyz, voxel_size, offsets, use_abs_xyz, with_dist):
+    """The per-point rows of dynamic_pillar_vfe.py:110-129, [K, F], straight into the layout the first Linear reads."""
+    points = points.contiguous()
+    width = points.shape[1]
+    f = width - (1 if use_abs_xyz else 4) + 6 + int(bool(with_dist))
+    out = torch.empty((index.K, f), dtype=torch.float32, device=points.device)
+    rc = L.load().toda_dynvox_pillar_decorate(L.ptr(points), width, L.ptr(index.rows), L.ptr(index.inv), L.ptr(index.coords),
+                                              L.ptr(mean_xyz.contiguous()), index.K, L.hptr(L.host_f32(voxel_size[:2])),
+                                              L.hptr(L.host_f32(offsets)), int(bool(use_abs_xyz)), int(bool(with_dist)), L.ptr(out), f,
+                                              L.stream())
+    L.check(rc, "toda_dynvox_pillar_decorate")
+    return out
+
+
+def dyn_seg_max_raw(x, index):
+    """(x_max [M, C], argmax [M, C] int32): torch_scatter.scatter_max; a tie goes to the lowest row."""
+    x = x.contiguous()
+    c = x.shape[1]
+    out = torch.empty((index.M, c), dtype=torch.float32, device=x.device)
+    arg = torch.empty((index.M, c), dtype=torch.int32, device=x.device)
+    rc = L.load().toda_dynvox_seg_max_fwd(L.ptr(x), c, L.ptr(index.seg_off), L.ptr(index.seg_pts), index.M, L.ptr(out), L.ptr(arg),
+                                          L.stream())
+    L.check(rc, "toda_dynvox_seg_max_fwd")
+    return out, arg
+
+
+class _DynSegMax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, index):
+        out, arg = dyn_seg_max_raw(x, index)
+        ctx.save_for_backward(arg)
+        ctx.meta = (x.shape[0], x.shape[1], index.M)
+        ctx.mark_non_differentiable(arg)
+        return out, arg
+
+    @staticmethod
+    def backward(ctx, gout, _garg):
+        (arg,) = ctx.saved_tensors
+        k, c, m = ctx.meta
+        gx = torch.empty((k, c), dtype=torch.float32, device=arg.device)
+        gout = gout.contiguous()
+        L.check(L.load().toda_dynvox_seg_max_bwd(L.ptr(gout), L.ptr(arg), m, c, k, L.ptr(gx), L.stream()), "toda_dynvox_seg_max_bwd")
+        return gx, None
+
+
+def dyn_seg_max(x, index):
+    """Differentiable scatter_max over the voxels of `index`: (x_max, argmax)."""
+    return _DynSegMax.apply(x, index)
+
+
+class _DynGatherConcat(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, x_max, index):
+        x = x.contiguous()
+        k, c = x.shape
+        out = torch.empty((k, 2 * c), dtype=torch.float32, device=x.device)
+        rc = L.load().toda_dynvox_gather_concat(L.ptr(x), L.ptr(x_max.contiguous()), L.ptr(index.inv), k, c, L.ptr(out), L.stream())
+        L.check(rc, "toda_dynvox_gather_concat")
+        ctx.index = index
+        ctx.c = c
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        g = g.contiguous()
+        c = ctx.c
+        # the gathered half: summed over each voxel's rows in seg_pts order
+        gmax = dyn_seg_sum(g, ctx.index, col0=c, ncol=c)
+        return g[:, :c], gmax, None
+
+
+def dyn_gather_concat(x, x_max, index):
+    """torch.cat([x, x_max[unq_inv]], dim=1) with its backward."""
+    return _DynGatherConcat.apply(x, x_max, index)
+
+
 # ------------------------------------------------------------------------------- rulebooks
 class GridIndex:
     """Bitmap + rank dictionary of one sparse level (device workspace)."""

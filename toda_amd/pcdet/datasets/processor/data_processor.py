@@ -68,20 +68,25 @@ class DataProcessor:
                 data_dict["points"] = pts[order]
         return data_dict
 
-    def _bind_voxel_geometry(self, config):
+    def _bind_voxel_geometry(self, config, dynamic=False):
         extent = (self.point_cloud_range[3:6] - self.point_cloud_range[0:3]).astype(np.float64)
         self.grid_size = np.round(extent / np.array(config.VOXEL_SIZE, dtype=np.float64)).astype(np.int64)
         self.voxel_size = list(config.VOXEL_SIZE)
         self.voxel_cfg = {
             "point_cloud_range": [float(v) for v in self.point_cloud_range],
             "voxel_size": [float(v) for v in config.VOXEL_SIZE],
-            "max_points_per_voxel": int(config.MAX_POINTS_PER_VOXEL),
-            "max_num_voxels": int(config.MAX_NUMBER_OF_VOXELS[self.mode]),
         }
+        if dynamic:
+            # dynamic voxelisation (DynPillarVFE / DynMeanVFE): no caps, the VFE groups the points itself
+            self.voxel_cfg["dynamic"] = True
+        else:
+            self.voxel_cfg["max_points_per_voxel"] = int(config.MAX_POINTS_PER_VOXEL)
+            self.voxel_cfg["max_num_voxels"] = int(config.MAX_NUMBER_OF_VOXELS[self.mode])
 
     def transform_points_to_voxels_placeholder(self, data_dict=None, config=None):
+        """The dynamic VFEs' processor (reference data_processor.py:138-143): binds range, voxel size and grid, voxelises nothing."""
         if data_dict is None:
-            self._bind_voxel_geometry(config)
+            self._bind_voxel_geometry(config, dynamic=True)
             return partial(self.transform_points_to_voxels_placeholder, config=config)
         return data_dict
 

@@ -31,11 +31,18 @@ def load_data_to_gpu(batch_dict):
             batch_dict[key] = torch.from_numpy(val).float().cuda(non_blocking=True)
 
 
+def is_dynamic(voxel_cfg):
+    """True for the geometry of transform_points_to_voxels_placeholder (DynPillarVFE / DynMeanVFE configs)."""
+    return bool(voxel_cfg is not None and voxel_cfg.get("dynamic", False))
+
+
 def voxelize_on_gpu(batch_dict, voxel_cfg):
     """points [sum N, 1 + C] (batch index in column 0) -> voxels / voxel_coords / voxel_num_points.
     voxel_cfg: dict(point_cloud_range, voxel_size, max_points_per_voxel, max_num_voxels)."""
     from ... import ops
 
+    if is_dynamic(voxel_cfg):
+        return batch_dict        # dynamic VFEs group the raw points themselves: no hard voxelisation
     pts = batch_dict["points"]
     bs = int(batch_dict["batch_size"])
     counts = batch_dict.get("points_per_sample")
@@ -59,10 +66,17 @@ def prepare_batch_on_gpu(batch_dict, net, voxel_cfg=None):
     backbone = getattr(net, "backbone_3d", None)
     if "voxels" not in batch_dict and "points" in batch_dict:
         cfg = voxel_cfg if voxel_cfg is not None else net.dataset.voxel_cfg
-        # voxels AND rulebooks behind one host sync when the backbone can plan from raw points
-        if backbone is not None and hasattr(backbone, "plan_input") and backbone.plan_input(batch_dict, cfg):
-            return batch_dict
-        voxelize_on_gpu(batch_dict, cfg)
+        if is_dynamic(cfg):
+            # the dynamic VFE's point index (one host read) on this stream - the input pipeline's side stream under InputPrefetcher -
+            # with voxel_coords, so that plan() below builds a sparse backbone's rulebooks before the forward
+            vfe = getattr(net, "vfe", None)
+            if vfe is not None and hasattr(vfe, "index_points") and batch_dict["points"].is_cuda:
+                vfe.index_points(batch_dict)
+        else:
+            # voxels AND rulebooks behind one host sync when the backbone can plan from raw points
+            if backbone is not None and hasattr(backbone, "plan_input") and backbone.plan_input(batch_dict, cfg):
+                return batch_dict
+            voxelize_on_gpu(batch_dict, cfg)
     if backbone is not None and hasattr(backbone, "plan") and "voxel_coords" in batch_dict and batch_dict["voxel_coords"].is_cuda:
         backbone.plan(batch_dict)
     return batch_dict

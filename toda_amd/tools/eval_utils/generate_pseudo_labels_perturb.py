@@ -81,6 +81,9 @@ def voxel_gradients(model, batch_points, pred_dicts, dataset, score_thresh):
 def inference_and_generate_pseudo_labes(cfg, args, model, dataloader, logger, dist_test=False, save_to_file=False, result_dir=None,
                                         unlabel_infos_path=None, optimizer=None):
     dataset = dataloader.dataset
+    if dataset.voxel_cfg is not None and dataset.voxel_cfg.get("dynamic", False):
+        raise NotImplementedError("voxel-perturbed pseudo labels need hard voxels (the gradient is taken w.r.t. `voxels`); a dynamic-VFE "
+                                  "configuration (transform_points_to_voxels_placeholder) has none")
     result_dir.mkdir(parents=True, exist_ok=True)
     logger.info("*************** INFERENCING UNLABELD INFOS (with voxel perturbations) *****************")
     start = time.time()
