@@ -422,6 +422,22 @@ int toda_nms_rotated(const float* boxes_sorted, int n, float thresh, int64_t* ke
                      int32_t* n_keep_dev, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * SECONDHead (pcdet/models/roi_heads/second_head.py, proposal_target_layer.py).
+ * toda_roi_grid_pool_bev: the rotated-RoI grid pool of second_head.py:53-110 in one launch for the batch - for roi r of sample
+ * r / N, F.affine_grid (align_corners=False) of its 2 x 3 matrix, then F.grid_sample (bilinear, zero padding) of the map.
+ * feat [B, C, H, W] fp32 NCHW; rois [B, N, roi_stride >= 7] (x, y, z, dx, dy, dz, heading, ...); step_x / step_y = voxel size x
+ * DOWNSAMPLE_RATIO; out [B * N, C, G, G] fp32, fully written.  Forward only (the reference detaches both inputs); no atomics.
+ * toda_roi_iou3d_max: per roi, the best 3-D IoU against the valid gts of its sample and the index of that gt
+ * (proposal_target_layer.py:92-96 + get_max_iou_with_same_class :194-228).  gt [B, M, gt_stride >= 8], label in the last
+ * column; valid gts = last row with a non-zero sum + 1, at least one.  by_class: only gts whose (long) label equals the roi's
+ * label (roi_labels [B, N] int64, may be NULL otherwise).  No eligible gt: IoU 0, index 0; ties: the lowest gt index.
+ * ---------------------------------------------------------------------- */
+int toda_roi_grid_pool_bev(const float* feat, int B, int C, int H, int W, const float* rois, int N, int roi_stride,
+                           float min_x, float min_y, float step_x, float step_y, int grid_size, float* out, void* stream);
+int toda_roi_iou3d_max(const float* rois, int B, int N, int roi_stride, const int64_t* roi_labels, const float* gt, int M,
+                       int gt_stride, int by_class, float* max_iou /*[B, N]*/, int64_t* argmax /*[B, N]*/, void* stream);
+
+/* ------------------------------------------------------------------------
  * Point-table primitives of the TODA mixing processors and the data processor's range mask.
  * They replace, on the device, the numpy / single-thread C++ work the reference does per scene in
  * DataLoader workers:

@@ -1826,6 +1826,41 @@ def nms_rotated(boxes_sorted, thresh):
     return keep, n_keep
 
 
+# ------------------------------------------------------------------ SECONDHead (RoI grid pool, 3-D IoU max per roi)
+def roi_grid_pool(features, rois, min_x, min_y, voxel_x, voxel_y, downsample_ratio, grid_size):
+    """BEV map [B, C, H, W] fp32 + rois [B, N, 7 + ...] -> [B * N, C, G, G] (second_head.py:53-110: affine_grid + grid_sample
+    per sample, align_corners=False, bilinear, zero padding).  Forward only: the result does not require grad."""
+    lib = L.load()
+    feat = features.detach().contiguous()
+    r = rois.detach().contiguous().float()
+    if feat.dtype != torch.float32 or feat.dim() != 4 or r.dim() != 3 or r.shape[0] != feat.shape[0]:
+        raise RuntimeError("roi_grid_pool: features [B, C, H, W] fp32 and rois [B, N, >= 7]")
+    b, c, h, w = feat.shape
+    n, g = r.shape[1], int(grid_size)
+    out = torch.empty((b * n, c, g, g), dtype=torch.float32, device=feat.device)
+    rc = lib.toda_roi_grid_pool_bev(L.ptr(feat), b, c, h, w, L.ptr(r), n, r.shape[2], float(min_x), float(min_y),
+                                    float(voxel_x * downsample_ratio), float(voxel_y * downsample_ratio), g, L.ptr(out), L.stream())
+    L.check(rc, "toda_roi_grid_pool_bev")
+    return out
+
+
+def roi_iou3d_max(rois, roi_labels, gt_boxes, by_class):
+    """rois [B, N, 7 + ...], roi_labels [B, N] (long), gt_boxes [B, M, 7 + ... + label] -> (max_iou [B, N] fp32,
+    gt index [B, N] int64) over the valid gts of each sample, restricted to gts of the roi's class when by_class."""
+    lib = L.load()
+    r = rois.detach().contiguous().float()
+    gt = gt_boxes.detach().contiguous().float()
+    lab = roi_labels.detach().contiguous().long() if roi_labels is not None else None
+    b, n = r.shape[0], r.shape[1]
+    m = gt.shape[1]
+    iou = torch.empty((b, n), dtype=torch.float32, device=r.device)
+    idx = torch.empty((b, n), dtype=torch.int64, device=r.device)
+    rc = lib.toda_roi_iou3d_max(L.ptr(r), b, n, r.shape[2], L.ptr(lab), L.ptr(gt) if m else None, m, gt.shape[2],
+                                int(bool(by_class)), L.ptr(iou), L.ptr(idx), L.stream())
+    L.check(rc, "toda_roi_iou3d_max")
+    return iou, idx
+
+
 # --------------------------------------------------------------------------- point tables (mix processors, range mask)
 def _rows(points, n_dev):
     if points.dtype != torch.float32 or points.dim() != 2:

@@ -1,12 +1,14 @@
 from .centerpoint import CenterPoint
 from .detector3d_template import Detector3DTemplate
 from .second_net import PointPillar, SECONDNet
+from .second_net_iou import SECONDNetIoU
 
 __all__ = {
     "Detector3DTemplate": Detector3DTemplate,
     "SECONDNet": SECONDNet,
     "PointPillar": PointPillar,
     "CenterPoint": CenterPoint,
+    "SECONDNetIoU": SECONDNetIoU,
 }
 
 

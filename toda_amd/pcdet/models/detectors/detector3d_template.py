@@ -1,14 +1,14 @@
 """Detector3DTemplate (reference pcdet/models/detectors/detector3d_template.py:14-411): module
 topology, registry-driven builders, checkpoint loading with the spconv-1.x -> 2.x weight layout
-conversion.  Only the voxel / pillar single-stage topology is populated (pfe / point_head /
-roi_head builders return None: out of scope)."""
+conversion.  The voxel / pillar topology is populated, with the registered RoI heads (roi_heads.__all__) on top; the pfe /
+point_head builders refuse their sections (point-based detectors: out of scope)."""
 import os
 
 import torch
 import torch.nn as nn
 
 from ...utils.spconv_utils import find_all_spconv_keys
-from .. import backbones_2d, backbones_3d, dense_heads
+from .. import backbones_2d, backbones_3d, dense_heads, roi_heads
 from ..backbones_2d import map_to_bev
 from ..backbones_3d import vfe
 
@@ -139,7 +139,18 @@ class Detector3DTemplate(nn.Module):
         return self._unsupported("POINT_HEAD", model_info_dict)
 
     def build_roi_head(self, model_info_dict):
-        return self._unsupported("ROI_HEAD", model_info_dict)
+        cfg = self._section("ROI_HEAD")
+        if cfg is None:
+            return None, model_info_dict
+        if cfg.NAME not in roi_heads.__all__:
+            raise NotImplementedError(f"MODEL.ROI_HEAD {cfg.NAME}: only {sorted(roi_heads.__all__)} are on this path (DESIGN.md)")
+        m = roi_heads.__all__[cfg.NAME](
+            model_cfg=cfg, input_channels=model_info_dict["num_bev_features"],
+            backbone_channels=model_info_dict.get("backbone_channels", None),
+            point_cloud_range=model_info_dict["point_cloud_range"], voxel_size=model_info_dict["voxel_size"],
+            num_class=self.num_class if not cfg.CLASS_AGNOSTIC else 1)
+        model_info_dict["module_list"].append(m)
+        return m, model_info_dict
 
     def forward(self, **kwargs):
         raise NotImplementedError
@@ -175,8 +186,8 @@ class Detector3DTemplate(nn.Module):
 
     @staticmethod
     def generate_recall_record(box_preds, recall_dict, batch_index, data_dict=None, thresh_list=None):
-        """#gt boxes whose best 3-D IoU with a prediction exceeds each threshold (reference :286-328); trailing all-zero
-        rows of the padded gt tensor are ignored, as there."""
+        """#gt boxes whose best 3-D IoU with a prediction (rcnn_*) or, for two-stage detectors, with a roi (roi_*) exceeds each
+        threshold (reference :286-328); trailing all-zero rows of the padded gt tensor are ignored, as there."""
         from ...ops.iou3d_nms import iou3d_nms_utils
 
         if "gt_boxes" not in data_dict:
@@ -196,6 +207,11 @@ class Detector3DTemplate(nn.Module):
                 best = iou3d_nms_utils.boxes_iou3d_gpu(box_preds[:, 0:7].contiguous(), gt[:, 0:7].contiguous()).max(dim=0)[0]
                 for t in thresh_list:
                     recall_dict[f"rcnn_{t}"] += int((best > t).sum().item())
+            if "rois" in data_dict:
+                rois = data_dict["rois"][batch_index]
+                best = iou3d_nms_utils.boxes_iou3d_gpu(rois[:, 0:7].contiguous(), gt[:, 0:7].contiguous()).max(dim=0)[0]
+                for t in thresh_list:
+                    recall_dict[f"roi_{t}"] += int((best > t).sum().item())
             recall_dict["gt"] += gt.shape[0]
         return recall_dict
 
