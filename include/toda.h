@@ -438,6 +438,39 @@ int toda_roi_iou3d_max(const float* rois, int B, int N, int roi_stride, const in
                        int gt_stride, int by_class, float* max_iou /*[B, N]*/, int64_t* argmax /*[B, N]*/, void* stream);
 
 /* ------------------------------------------------------------------------
+ * VoxelRCNNHead (pcdet/models/roi_heads/voxelrcnn_head.py, ops/pointnet2/pointnet2_stack/voxel_{query_utils,pool_modules}.py).
+ * toda_voxel_query: voxel_query_gpu.cu's scan (dz, dy, dx over [-range, range], keep dist2 <= radius^2 in scan order, the
+ * first hit fills the row, stop at nsample hits) over one level.  new_xyz [M, 3] fp32, new_coords [M, 4] int32 (b, z, y, x);
+ * xyz [N, 3] voxel centres of the level's rows; gi = the level's grid-index buffer (toda_gridindex_*), rowof its rank -> row
+ * map or NULL when the ranks are the rows; shape_host = (Z, Y, X), ranges_host = (z, y, x).  idx [M, nsample] int32 = rows of
+ * the level (all zero for an empty ball), empty [M] uint8.  Grid points with b outside [0, batch) get empty balls.
+ * toda_voxel_pool_moments: mean (3) and biased covariance (3 x 3) of d = xyz[idx] - new_xyz (0 for empty balls) over all
+ * M x nsample entries, fp64, fixed-order; ws [toda_voxel_pool_moments_doubles()] doubles, the result in ws[0:12].
+ * toda_voxel_pool_fwd: out[m, c] = max_s relu(f[idx[m, s], c] [not empty] + ab[c, 0:3] . d_ms + ab[c, 3]); f [N, C], ab [C, 4],
+ * out [M, C]; arg [M, C] uint8 (NULL: not stored) = first arg-max s, 0xff where out is 0.
+ * toda_voxel_pool_table: the inverse neighbour table of idx: off [N + 1] (exclusive prefix of the per-row counts), ent [M x
+ * nsample] = entries m * nsample + s of row n at ent[off[n] .. off[n + 1]), ascending; empty balls are left out.
+ * toda_voxel_pool_bwd_feat: gf [N, C] = d out / d f through the table; toda_voxel_pool_bwd_pos: gab [C, 4] = d out / d ab,
+ * ws [toda_voxel_pool_bwd_pos_doubles(C)] doubles.  Integer atomics only: every result is bit-reproducible.
+ * ---------------------------------------------------------------------- */
+int toda_voxel_query(const float* new_xyz, const int32_t* new_coords, int M, const float* xyz, int N, const void* gi, const int32_t* rowof,
+                     int batch, const int32_t* shape_host, float radius, const int32_t* ranges_host, int nsample, int32_t* idx,
+                     uint8_t* empty, void* stream);
+size_t toda_voxel_pool_moments_doubles(void);
+int toda_voxel_pool_moments(const int32_t* idx, const uint8_t* empty, int M, int nsample, const float* xyz, int N, const float* new_xyz,
+                            double* ws, void* stream);
+int toda_voxel_pool_fwd(const float* f, int N, int C, const int32_t* idx, const uint8_t* empty, int M, int nsample, const float* xyz,
+                        const float* new_xyz, const float* ab, float* out, uint8_t* arg, void* stream);
+size_t toda_voxel_pool_table_bytes(int M, int nsample, int N);
+int toda_voxel_pool_table(const int32_t* idx, const uint8_t* empty, int M, int nsample, int N, int32_t* off, int32_t* ent, void* ws,
+                          size_t ws_bytes, void* stream);
+int toda_voxel_pool_bwd_feat(const float* gout, const uint8_t* arg, int M, int nsample, int C, const int32_t* off, const int32_t* ent,
+                             int N, float* gf, void* stream);
+size_t toda_voxel_pool_bwd_pos_doubles(int C);
+int toda_voxel_pool_bwd_pos(const float* gout, const uint8_t* arg, const int32_t* idx, const uint8_t* empty, int M, int nsample, int C,
+                            const float* xyz, int N, const float* new_xyz, double* ws, float* gab, void* stream);
+
+/* ------------------------------------------------------------------------
  * Point-table primitives of the TODA mixing processors and the data processor's range mask.
  * They replace, on the device, the numpy / single-thread C++ work the reference does per scene in
  * DataLoader workers:

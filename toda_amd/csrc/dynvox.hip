@@ -16,14 +16,11 @@
 // Every reduction after that reads its segment in seg_pts order with one thread per (voxel, column): no atomics, the same
 // order on every run, bit-reproducible.  Integer atomics only (bitmap bits, LDS histograms); no float atomic in this file.
 // Byte-bound index work: ~70 B per point plus the bitmap (2 bits of words + prefixes per key-space cell, memset per call).
-#include "scan.cuh"
+#include "radix_sort.cuh"
 
 namespace toda {
 
 constexpr int DV_BLOCK = 256;
-constexpr int RS_ITEMS = 8;
-constexpr int RS_TILE = DV_BLOCK * RS_ITEMS;      // elements per radix-sort workgroup
-constexpr int RS_BINS = 256;
 
 struct DvGeom {
     float r0[3];
@@ -82,68 +79,6 @@ dv_rank_kernel(const float* __restrict__ pts, int n, int width, DvGeom g, const 
     sort_key[r] = v;
     sort_val[r] = r;
     row_key[r] = key;
-}
-
-// ---- stable LSD radix sort of (key, val), 8 bits per pass --------------------------------------------------------------------
-__global__ void __launch_bounds__(DV_BLOCK)
-rs_hist_kernel(const int32_t* __restrict__ key, int n, int shift, int nblk, int32_t* __restrict__ hist) {
-    __shared__ int s_h[RS_BINS];
-    s_h[threadIdx.x] = 0;
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < RS_ITEMS; ++j) {
-        const int i = blockIdx.x * RS_TILE + j * DV_BLOCK + threadIdx.x;
-        if (i < n) atomicAdd(&s_h[((unsigned)key[i] >> shift) & 255u], 1);
-    }
-    __syncthreads();
-    hist[(size_t)threadIdx.x * nblk + blockIdx.x] = s_h[threadIdx.x];     // digit-major: the scan gives digit, then block order
-}
-
-// element i of the tile goes to hist[digit][block] + (# earlier elements of the tile with that digit): rounds of 256 elements in
-// index order; inside a round the wave peers of a digit (8 ballots) and the per-wave digit counts of the earlier waves.
-__global__ void __launch_bounds__(DV_BLOCK)
-rs_scatter_kernel(const int32_t* __restrict__ key_in, const int32_t* __restrict__ val_in, int n, int shift, int nblk,
-                  const int32_t* __restrict__ hist, int32_t* __restrict__ key_out, int32_t* __restrict__ val_out) {
-    __shared__ int s_base[RS_BINS];
-    __shared__ int s_wc[DV_BLOCK / 64][RS_BINS];
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    s_base[t] = hist[(size_t)t * nblk + blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < DV_BLOCK / 64; ++k) s_wc[k][t] = 0;
-    __syncthreads();
-    const unsigned long long below = (1ull << lane) - 1ull;
-    for (int j = 0; j < RS_ITEMS; ++j) {
-        const int i = blockIdx.x * RS_TILE + j * DV_BLOCK + t;
-        const bool valid = i < n;
-        const int k = valid ? key_in[i] : 0;
-        const int vv = valid ? val_in[i] : 0;
-        const unsigned d = ((unsigned)k >> shift) & 255u;
-        unsigned long long peers = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const bool on = (d >> b) & 1u;
-            const unsigned long long bb = __ballot(valid && on);
-            peers &= on ? bb : ~bb;
-        }
-        const int rank = __popcll(peers & below);
-        if (valid && rank == 0) s_wc[w][d] = __popcll(peers);
-        __syncthreads();
-        if (valid) {
-            int off = s_base[d] + rank;
-            for (int q = 0; q < w; ++q) off += s_wc[q][d];
-            key_out[off] = k;
-            val_out[off] = vv;
-        }
-        __syncthreads();
-        int add = 0;
-#pragma unroll
-        for (int q = 0; q < DV_BLOCK / 64; ++q) {
-            add += s_wc[q][t];
-            s_wc[q][t] = 0;
-        }
-        s_base[t] += add;
-        __syncthreads();
-    }
 }
 
 __global__ void __launch_bounds__(DV_BLOCK)

@@ -96,6 +96,15 @@ SIGNATURES = {
     "toda_nms_rotated": (_i, [_vp, _i, C.c_float, _vp, _vp, _vp, _sz, _vp]),
     "toda_roi_grid_pool_bev": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, C.c_float, C.c_float, C.c_float, C.c_float, _i, _vp, _vp]),
     "toda_roi_iou3d_max": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "toda_voxel_query": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, C.c_float, _vp, _i, _vp, _vp, _vp]),
+    "toda_voxel_pool_moments_doubles": (_sz, []),
+    "toda_voxel_pool_moments": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "toda_voxel_pool_fwd": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "toda_voxel_pool_table_bytes": (_sz, [_i, _i, _i]),
+    "toda_voxel_pool_table": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "toda_voxel_pool_bwd_feat": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    "toda_voxel_pool_bwd_pos_doubles": (_sz, [_i]),
+    "toda_voxel_pool_bwd_pos": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "toda_clip_adam_chunk": (_i, []),
     "toda_clip_adam_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _i, _vp]),
     "toda_points_in_boxes": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _vp]),

@@ -1861,6 +1861,106 @@ def roi_iou3d_max(rois, roi_labels, gt_boxes, by_class):
     return iou, idx
 
 
+# --------------------------------------------------------------------------- voxel query + neighbour pool (VoxelRCNNHead)
+def voxel_query(new_xyz, new_coords, xyz, grid_index, radius, query_range, nsample):
+    """The voxel query of one level (reference voxel_query_utils.py:12-44 + src/voxel_query_gpu.cu:10-91): for every grid point
+    new_xyz [M, 3] with lattice coordinates new_coords [M, 4] int32 (b, z, y, x), the rows of the level (voxel centres xyz [N, 3])
+    within `radius`, scanning dz, dy, dx over [-range, range] with query_range = (z, y, x) as the reference unpacks it.  Membership
+    and rows come from the level's GridIndex (bitmap + rank, rowof when set) instead of the reference's dense [B, Z, Y, X]
+    table.  Returns idx [M, nsample] int32 - rows of the level's feature table (the reference's batch-local index plus the
+    batch's first row), the first hit filling the row, zeros for an empty ball - and empty [M] bool."""
+    lib = L.load()
+    nx = new_xyz.detach().contiguous()
+    nc = new_coords.detach().contiguous()
+    v = xyz.detach().contiguous()
+    if nx.dtype != torch.float32 or v.dtype != torch.float32 or nc.dtype != torch.int32 or nc.dim() != 2 or nc.shape[1] != 4 \
+            or nx.shape != (nc.shape[0], 3) or v.dim() != 2 or v.shape[1] != 3:
+        raise RuntimeError("voxel_query: new_xyz [M, 3] fp32, new_coords [M, 4] int32, xyz [N, 3] fp32")
+    m, n, ns = nc.shape[0], v.shape[0], int(nsample)
+    idx = torch.empty((m, ns), dtype=torch.int32, device=nx.device)
+    empty = torch.empty((m,), dtype=torch.bool, device=nx.device)
+    shape_c = L.host_i32(grid_index.shape)
+    rng_c = L.host_i32([int(r) for r in query_range])
+    rc = lib.toda_voxel_query(L.ptr(nx), L.ptr(nc), m, L.ptr(v) if n else None, n, L.ptr(grid_index.buf), L.ptr(grid_index.rowof),
+                              grid_index.batch, L.hptr(shape_c), float(radius), L.hptr(rng_c), ns, L.ptr(idx), L.ptr(empty), L.stream())
+    L.check(rc, "toda_voxel_query")
+    return idx, empty
+
+
+def voxel_pool_moments(idx, empty, xyz, new_xyz):
+    """Mean [3] and biased covariance [3, 3] (fp64) of the relative positions d = xyz[idx] - new_xyz (0 for empty balls) over all
+    M x nsample entries: the statistics BatchNorm2d of mlps_pos sees through its Conv2d (reference voxel_pool_modules.py:110-115)."""
+    lib = L.load()
+    m, ns = idx.shape
+    ws = torch.empty((lib.toda_voxel_pool_moments_doubles(),), dtype=torch.float64, device=idx.device)
+    rc = lib.toda_voxel_pool_moments(L.ptr(idx), L.ptr(empty), m, ns, L.ptr(xyz) if xyz.shape[0] else None, xyz.shape[0],
+                                     L.ptr(new_xyz), L.ptr(ws), L.stream())
+    L.check(rc, "toda_voxel_pool_moments")
+    return ws[0:3], ws[3:12].view(3, 3)
+
+
+class _VoxelPool(torch.autograd.Function):
+    """out [M, C] = max_s relu(f[idx[m, s]] [not empty] + a . d_ms + b) (toda_voxel_pool_fwd); backward: d f through the inverse
+    neighbour table built here in the forward (toda_voxel_pool_table, toda_voxel_pool_bwd_feat), d a / d b by fixed-order
+    partial sums (toda_voxel_pool_bwd_pos).  ab [C, 4] = (a_x, a_y, a_z, b)."""
+
+    @staticmethod
+    def forward(ctx, f, ab, idx, empty, xyz, new_xyz):
+        lib = L.load()
+        f = f.contiguous()
+        ab = ab.contiguous()
+        n, c = f.shape
+        m, ns = idx.shape
+        need_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        out = torch.empty((m, c), dtype=torch.float32, device=f.device)
+        arg = torch.empty((m, c), dtype=torch.uint8, device=f.device) if need_grad else None
+        rc = lib.toda_voxel_pool_fwd(L.ptr(f) if n else None, n, c, L.ptr(idx), L.ptr(empty), m, ns, L.ptr(xyz) if n else None,
+                                     L.ptr(new_xyz), L.ptr(ab), L.ptr(out), L.ptr(arg), L.stream())
+        L.check(rc, "toda_voxel_pool_fwd")
+        if need_grad:
+            off = torch.empty((n + 1,), dtype=torch.int32, device=f.device)
+            ent = torch.empty((max(m * ns, 1),), dtype=torch.int32, device=f.device)
+            nbytes = lib.toda_voxel_pool_table_bytes(m, ns, n)
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=f.device)
+            rc = lib.toda_voxel_pool_table(L.ptr(idx), L.ptr(empty), m, ns, n, L.ptr(off), L.ptr(ent), L.ptr(ws), nbytes, L.stream())
+            L.check(rc, "toda_voxel_pool_table")
+            ctx.save_for_backward(arg, idx, empty, xyz, new_xyz, off, ent)
+        ctx.meta = (n, c)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = L.load()
+        arg, idx, empty, xyz, new_xyz, off, ent = ctx.saved_tensors
+        n, c = ctx.meta
+        m, ns = idx.shape
+        g = g.contiguous()
+        gf = gab = None
+        if ctx.needs_input_grad[0]:
+            gf = torch.empty((n, c), dtype=torch.float32, device=g.device)
+            rc = lib.toda_voxel_pool_bwd_feat(L.ptr(g), L.ptr(arg), m, ns, c, L.ptr(off), L.ptr(ent), n, L.ptr(gf), L.stream())
+            L.check(rc, "toda_voxel_pool_bwd_feat")
+        if ctx.needs_input_grad[1]:
+            ws = torch.empty((lib.toda_voxel_pool_bwd_pos_doubles(c),), dtype=torch.float64, device=g.device)
+            gab = torch.empty((c, 4), dtype=torch.float32, device=g.device)
+            rc = lib.toda_voxel_pool_bwd_pos(L.ptr(g), L.ptr(arg), L.ptr(idx), L.ptr(empty), m, ns, c, L.ptr(xyz) if n else None, n,
+                                             L.ptr(new_xyz), L.ptr(ws), L.ptr(gab), L.stream())
+            L.check(rc, "toda_voxel_pool_bwd_pos")
+        return gf, gab, None, None, None, None
+
+
+def voxel_neighbor_pool(f, a, b, idx, empty, xyz, new_xyz):
+    """The grouping, position branch, ReLU and max pool of NeighborVoxelSAModuleMSG (reference voxel_pool_modules.py:96-125 and
+    voxel_query_utils.py:83-102: grouping_operation of features and xyz into [M, C, nsample] / [M, 3, nsample], the empty-ball
+    masks, mlps_pos, the sum, ReLU, F.max_pool2d over nsample) fused into one pass that never builds an [M, C, nsample] tensor.
+    f [N, C]: mlps_in output of the level's rows; a [C, 3], b [C]: mlps_pos folded into an affine map of d (differentiable);
+    idx / empty: voxel_query.  Returns [M, C]."""
+    if f.dtype != torch.float32 or f.dim() != 2 or a.shape != (f.shape[1], 3) or b.shape != (f.shape[1],) or idx.dim() != 2:
+        raise RuntimeError("voxel_neighbor_pool: f [N, C] fp32, a [C, 3], b [C], idx [M, nsample]")
+    ab = torch.cat([a, b.unsqueeze(1)], dim=1).float()
+    return _VoxelPool.apply(f, ab, idx.contiguous(), empty.contiguous(), xyz.detach().contiguous(), new_xyz.detach().contiguous())
+
+
 # --------------------------------------------------------------------------- point tables (mix processors, range mask)
 def _rows(points, n_dev):
     if points.dtype != torch.float32 or points.dim() != 2:

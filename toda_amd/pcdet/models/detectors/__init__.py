@@ -2,6 +2,7 @@ from .centerpoint import CenterPoint
 from .detector3d_template import Detector3DTemplate
 from .second_net import PointPillar, SECONDNet
 from .second_net_iou import SECONDNetIoU
+from .voxel_rcnn import VoxelRCNN
 
 __all__ = {
     "Detector3DTemplate": Detector3DTemplate,
@@ -9,6 +10,7 @@ __all__ = {
     "PointPillar": PointPillar,
     "CenterPoint": CenterPoint,
     "SECONDNetIoU": SECONDNetIoU,
+    "VoxelRCNN": VoxelRCNN,
 }
 
 

@@ -174,13 +174,18 @@ class Detector3DTemplate(nn.Module):
             raw_cls = batch_dict["batch_cls_preds"][pick]
             cls_preds = raw_cls if batch_dict["cls_preds_normalized"] else torch.sigmoid(raw_cls)
             scores, labels = torch.max(cls_preds, dim=-1)
-            labels = labels + 1
+            if batch_dict.get("has_class_labels", False):
+                # two-stage detectors: the labels of the rois the scores refine (reference :252-256)
+                labels = batch_dict["roi_labels" if "roi_labels" in batch_dict else "batch_pred_labels"][index]
+            else:
+                labels = labels + 1
             selected, selected_scores = model_nms_utils.class_agnostic_nms(box_scores=scores, box_preds=box_preds,
                                                                            nms_config=cfg.NMS_CONFIG, score_thresh=cfg.SCORE_THRESH)
             if cfg.get("OUTPUT_RAW_SCORE", False):
                 selected_scores = torch.max(raw_cls, dim=-1)[0][selected]
             final_boxes = box_preds[selected]
-            recall_dict = self.generate_recall_record(final_boxes, recall_dict, index, batch_dict, cfg.RECALL_THRESH_LIST)
+            recall_dict = self.generate_recall_record(final_boxes if "rois" not in batch_dict else box_preds, recall_dict, index, batch_dict,
+                                                      cfg.RECALL_THRESH_LIST)
             pred_dicts.append({"pred_boxes": final_boxes, "pred_scores": selected_scores, "pred_labels": labels[selected]})
         return pred_dicts, recall_dict
 

@@ -4,6 +4,7 @@ builder whose Conv1d / BatchNorm1d / Dropout keys the checkpoints carry."""
 import numpy as np
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from ...utils import box_coder_utils, common_utils, loss_utils
 from ..model_utils.model_nms_utils import class_agnostic_nms
@@ -92,6 +93,74 @@ class RoIHeadTemplate(nn.Module):
         gt_of_rois[:, :, 6] = torch.clamp(heading, min=-np.pi / 2, max=np.pi / 2)
         targets_dict["gt_of_rois"] = gt_of_rois
         return targets_dict
+
+    def get_box_reg_layer_loss(self, forward_ret_dict):
+        """Smooth-L1 of the residual-coded box in the roi's frame over the foreground rois, plus the corner regularisation of the
+        decoded box against the gt in the lidar frame (reference roi_head_template.py:136-196)."""
+        loss_cfgs = self.model_cfg.LOSS_CONFIG
+        code_size = self.box_coder.code_size
+        reg_valid_mask = forward_ret_dict["reg_valid_mask"].view(-1)
+        gt_boxes3d_ct = forward_ret_dict["gt_of_rois"][..., 0:code_size]
+        gt_of_rois_src = forward_ret_dict["gt_of_rois_src"][..., 0:code_size].view(-1, code_size)
+        rcnn_reg = forward_ret_dict["rcnn_reg"]
+        roi_boxes3d = forward_ret_dict["rois"]
+        rcnn_batch_size = gt_boxes3d_ct.view(-1, code_size).shape[0]
+        fg_mask = reg_valid_mask > 0
+        fg_sum = int(fg_mask.long().sum().item())
+        tb_dict = {}
+        if loss_cfgs.REG_LOSS != "smooth-l1":
+            raise NotImplementedError(f"REG_LOSS {loss_cfgs.REG_LOSS}")
+        rois_anchor = roi_boxes3d.clone().detach().view(-1, code_size)
+        rois_anchor[:, 0:3] = 0
+        rois_anchor[:, 6] = 0
+        reg_targets = self.box_coder.encode_torch(gt_boxes3d_ct.view(rcnn_batch_size, code_size), rois_anchor)
+        rcnn_loss_reg = self.reg_loss_func(rcnn_reg.view(rcnn_batch_size, -1).unsqueeze(dim=0), reg_targets.unsqueeze(dim=0))
+        rcnn_loss_reg = (rcnn_loss_reg.view(rcnn_batch_size, -1) * fg_mask.unsqueeze(dim=-1).float()).sum() / max(fg_sum, 1)
+        rcnn_loss_reg = rcnn_loss_reg * loss_cfgs.LOSS_WEIGHTS["rcnn_reg_weight"]
+        tb_dict["rcnn_loss_reg"] = rcnn_loss_reg.detach()
+        if loss_cfgs.CORNER_LOSS_REGULARIZATION and fg_sum > 0:
+            fg_rcnn_reg = rcnn_reg.view(rcnn_batch_size, -1)[fg_mask]
+            fg_roi_boxes3d = roi_boxes3d.view(-1, code_size)[fg_mask].view(1, -1, code_size)
+            batch_anchors = fg_roi_boxes3d.clone().detach()
+            roi_ry = fg_roi_boxes3d[:, :, 6].view(-1)
+            roi_xyz = fg_roi_boxes3d[:, :, 0:3].view(-1, 3)
+            batch_anchors[:, :, 0:3] = 0
+            rcnn_boxes3d = self.box_coder.decode_torch(fg_rcnn_reg.view(batch_anchors.shape[0], -1, code_size), batch_anchors).view(-1, code_size)
+            rcnn_boxes3d = common_utils.rotate_points_along_z(rcnn_boxes3d.unsqueeze(dim=1), roi_ry).squeeze(dim=1)
+            rcnn_boxes3d[:, 0:3] += roi_xyz
+            loss_corner = loss_utils.get_corner_loss_lidar(rcnn_boxes3d[:, 0:7], gt_of_rois_src[fg_mask][:, 0:7]).mean()
+            loss_corner = loss_corner * loss_cfgs.LOSS_WEIGHTS["rcnn_corner_weight"]
+            rcnn_loss_reg = rcnn_loss_reg + loss_corner
+            tb_dict["rcnn_loss_corner"] = loss_corner.detach()
+        return rcnn_loss_reg, tb_dict
+
+    def get_box_cls_layer_loss(self, forward_ret_dict):
+        """BinaryCrossEntropy on sigmoid(rcnn_cls) or CrossEntropy, averaged over the rois with a label >= 0 (reference
+        roi_head_template.py:198-216)."""
+        loss_cfgs = self.model_cfg.LOSS_CONFIG
+        rcnn_cls = forward_ret_dict["rcnn_cls"]
+        rcnn_cls_labels = forward_ret_dict["rcnn_cls_labels"].view(-1)
+        if loss_cfgs.CLS_LOSS == "BinaryCrossEntropy":
+            batch_loss_cls = F.binary_cross_entropy(torch.sigmoid(rcnn_cls.view(-1)), rcnn_cls_labels.float(), reduction="none")
+        elif loss_cfgs.CLS_LOSS == "CrossEntropy":
+            batch_loss_cls = F.cross_entropy(rcnn_cls, rcnn_cls_labels, reduction="none", ignore_index=-1)
+        else:
+            raise NotImplementedError(f"CLS_LOSS {loss_cfgs.CLS_LOSS}")
+        cls_valid_mask = (rcnn_cls_labels >= 0).float()
+        rcnn_loss_cls = (batch_loss_cls * cls_valid_mask).sum() / torch.clamp(cls_valid_mask.sum(), min=1.0)
+        rcnn_loss_cls = rcnn_loss_cls * loss_cfgs.LOSS_WEIGHTS["rcnn_cls_weight"]
+        return rcnn_loss_cls, {"rcnn_loss_cls": rcnn_loss_cls.detach()}
+
+    def get_loss(self, tb_dict=None):
+        """Classification + box regression losses of the refined rois (reference roi_head_template.py:218-229)."""
+        tb_dict = {} if tb_dict is None else tb_dict
+        rcnn_loss_cls, cls_tb_dict = self.get_box_cls_layer_loss(self.forward_ret_dict)
+        tb_dict.update(cls_tb_dict)
+        rcnn_loss_reg, reg_tb_dict = self.get_box_reg_layer_loss(self.forward_ret_dict)
+        tb_dict.update(reg_tb_dict)
+        rcnn_loss = rcnn_loss_cls + rcnn_loss_reg
+        tb_dict["rcnn_loss"] = rcnn_loss.detach()
+        return rcnn_loss, tb_dict
 
     def generate_predicted_boxes(self, batch_size, rois, cls_preds, box_preds):
         """Decode box_preds [B * N, code] relative to the rois (local frame, then rotated and shifted back)."""

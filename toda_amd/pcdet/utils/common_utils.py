@@ -121,6 +121,16 @@ def rotate_points_along_z(points, angle):
     return out.numpy() if is_numpy else out
 
 
+def get_voxel_centers(voxel_coords, downsample_times, voxel_size, point_cloud_range):
+    """Centres (x, y, z) of voxels given as (z, y, x) coordinates [N, 3] of a level downsampled `downsample_times` times, in fp32
+    (reference common_utils.py:66-82)."""
+    assert voxel_coords.shape[1] == 3
+    voxel_centers = voxel_coords[:, [2, 1, 0]].float()
+    voxel_size = torch.tensor(voxel_size, device=voxel_centers.device).float() * downsample_times
+    pc_range = torch.tensor(point_cloud_range[0:3], device=voxel_centers.device).float()
+    return (voxel_centers + 0.5) * voxel_size + pc_range
+
+
 def merge_results_dist(result_part, size, tmpdir=None):
     """Gather per-rank result lists in dataset order (reference common_utils.py:205-238 does this through pickles in a
     shared tmpdir; here one all_gather_object over the process group).  The evaluation sampler deals indices round

@@ -1,5 +1,6 @@
 """Losses on the dense-head path (reference pcdet/utils/loss_utils.py): CenterNet focal + masked L1
 (:264-385) and the anchor-head trio sigmoid-focal / weighted smooth-L1 / weighted CE (:9-206)."""
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -119,3 +120,19 @@ class WeightedCrossEntropyLoss(nn.Module):
         """input [B, A, C] logits, target [B, A, C] one-hot, weights [B, A] -> [B, A]"""
         loss = F.cross_entropy(input.permute(0, 2, 1), target.argmax(dim=-1), reduction="none")
         return loss * weights
+
+
+# ------------------------------------------------------------------ RoI-head corner regularisation
+def get_corner_loss_lidar(pred_bbox3d, gt_bbox3d):
+    """Smooth-L1 (beta 1) of the distance between matching corners of pred and gt [N, 7], taking for every corner the nearer of
+    the gt and its heading-flipped copy, averaged over the 8 corners -> [N] (reference loss_utils.py:209-232)."""
+    from . import box_utils
+
+    assert pred_bbox3d.shape[0] == gt_bbox3d.shape[0]
+    pred_corners = box_utils.boxes_to_corners_3d(pred_bbox3d)
+    gt_corners = box_utils.boxes_to_corners_3d(gt_bbox3d)
+    gt_flip = gt_bbox3d.clone()
+    gt_flip[:, 6] += np.pi
+    gt_corners_flip = box_utils.boxes_to_corners_3d(gt_flip)
+    corner_dist = torch.min(torch.norm(pred_corners - gt_corners, dim=2), torch.norm(pred_corners - gt_corners_flip, dim=2))
+    return WeightedSmoothL1Loss.smooth_l1_loss(corner_dist, beta=1.0).mean(dim=1)
