@@ -44,6 +44,7 @@ extern "C" {
  * a wait that gives up raises its bit and the launch finishes with invalid numbers instead of hanging the GPU. */
 #define TODA_FAULT_BN2D 1u /* bn2d_fwd/bwd_split_kernel: partner never published */
 #define TODA_FAULT_WINO 2u /* wino_fwd_ws_kernel: stream-K contributor never published */
+#define TODA_FAULT_FPS 4u  /* fps_multi_kernel: a workgroup of the sample's group never arrived */
 
 const char* toda_last_error(void);
 /* ABI version of this header; bumped on any signature change. */
@@ -469,6 +470,49 @@ int toda_voxel_pool_bwd_feat(const float* gout, const uint8_t* arg, int M, int n
 size_t toda_voxel_pool_bwd_pos_doubles(int C);
 int toda_voxel_pool_bwd_pos(const float* gout, const uint8_t* arg, const int32_t* idx, const uint8_t* empty, int M, int nsample, int C,
                             const float* xyz, int N, const float* new_xyz, double* ws, float* gab, void* stream);
+
+/* ------------------------------------------------------------------------
+ * PV-RCNN's PointNet++ stack layer (pcdet/ops/pointnet2/pointnet2_stack, backbones_3d/pfe/voxel_set_abstraction.py).
+ * toda_fps: farthest point sampling of every sample of a stacked cloud xyz [N, 3]; starts_host [batch + 1] host offsets of the
+ * samples; idx [batch, npoint] int32 sample-local indices, equal to sampling_gpu.cu's farthest_point_sampling_kernel (first index
+ * 0, temp from 1e10, d = dx dx + dy dy + dz dz; ties to the smallest bit-reversed k mod opt_n_threads(n), the order its block
+ * tree prefers, then the smallest k).  mode 1: one
+ * workgroup per sample (temp [N] fp32 scratch); mode 2: co-resident workgroup groups meeting at a bounded inter-workgroup
+ * barrier (ws [toda_fps_workspace_bytes]; TODA_FAULT_FPS if a wait gives up); mode 0 picks by sample size and falls back to
+ * mode 1 when the groups do not fit toda_fps_resident_blocks().
+ * toda_ball_query_stack: for every query new_xyz [M, 3] (sample by new_start [batch + 1], device), the points of its sample
+ * (xyz_start [batch + 1], device) in ascending index with d2 < r^2, for nr nested radii in one scan: idx_host[r] [M, nsample_r]
+ * int32 rows of xyz (the first hit fills the row, stop at nsample_r hits; zeros for an empty ball), empty_host[r] [M] uint8.
+ * toda_sa_gather_fwd: layer 1 of a StackSAModuleMSG MLP after its feature GEMM: z [M x nsample, C] = P[idx] + wd [C, 3] . d,
+ * d = xyz[idx] - new_xyz, 0 for an empty ball.  Backward: gP [N, C] through the inverse neighbour table of
+ * toda_voxel_pool_table (toda_sa_gather_bwd_feat), gwd [C, 3] from fp64 partials (ws [toda_sa_gather_bwd_pos_doubles(C)]).
+ * toda_sa_max_fwd: out [M, C] = max over nsample of y [M x nsample, C], arg [M, C] uint8 the first arg-max (0xff where the
+ * maximum is 0); toda_sa_max_bwd: gy [M x nsample, C].
+ * toda_bev_interp_fwd: voxel_set_abstraction.py's bilinear_interpolate_torch from map [B, C, H, W] at xy [K, 2] (column, row)
+ * of sample bidx [K]: out [K, C]; taps [K, 4] pixel ids (b H + y) W + x of Ia Ib Ic Id and wts [K, 4] their weights (both NULL:
+ * not stored).  toda_bev_interp_bwd: gmap [B, C, H, W] through the pixel table of taps (toda_voxel_pool_table with
+ * M = K, nsample = 4, N = B H W).  No float atomics: every result is bit-reproducible.
+ * ---------------------------------------------------------------------- */
+int toda_fps_resident_blocks(void);
+size_t toda_fps_workspace_bytes(int batch, int npoint);
+int toda_fps(const float* xyz, const int32_t* starts_host, int batch, int npoint, int mode, float* temp, int32_t* idx, void* ws,
+             size_t ws_bytes, void* stream);
+int toda_ball_query_stack(const float* xyz, int N, const int32_t* xyz_start, const float* new_xyz, const int32_t* new_start, int batch,
+                          int M, int nr, const float* radii_host, const int32_t* nsample_host, int32_t* const* idx_host,
+                          uint8_t* const* empty_host, void* stream);
+int toda_sa_gather_fwd(const float* P, int N, int C, const float* wd, const int32_t* idx, const uint8_t* empty, int M, int nsample,
+                       const float* xyz, const float* new_xyz, float* z, void* stream);
+int toda_sa_gather_bwd_feat(const float* gz, int M, int nsample, int C, const int32_t* off, const int32_t* ent, int N, float* gP,
+                            void* stream);
+size_t toda_sa_gather_bwd_pos_doubles(int C);
+int toda_sa_gather_bwd_pos(const float* gz, const int32_t* idx, const uint8_t* empty, int M, int nsample, int C, const float* xyz, int N,
+                           const float* new_xyz, double* ws, float* gwd, void* stream);
+int toda_sa_max_fwd(const float* y, int M, int nsample, int C, float* out, uint8_t* arg, void* stream);
+int toda_sa_max_bwd(const float* g, const uint8_t* arg, int M, int nsample, int C, float* gy, void* stream);
+int toda_bev_interp_fwd(const float* map, int B, int C, int H, int W, const float* xy, const int32_t* bidx, int K, float* out,
+                        int32_t* taps, float* wts, void* stream);
+int toda_bev_interp_bwd(const float* g, int K, int C, const int32_t* off, const int32_t* ent, const float* wts, int B, int H, int W,
+                        float* gmap, void* stream);
 
 /* ------------------------------------------------------------------------
  * Point-table primitives of the TODA mixing processors and the data processor's range mask.

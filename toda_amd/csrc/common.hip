@@ -63,7 +63,8 @@ extern "C" int toda_abi_version(void) { return 3; }
 extern "C" int toda_device_fault(void) {
     const unsigned v = toda::fault_take();
     if (!v) return TODA_OK;
-    toda::set_error("device fault word 0x%x: a bounded inter-workgroup wait gave up (%s%s); the results of that launch are invalid",
-                    v, (v & TODA_FAULT_BN2D) ? "bn2d split kernel " : "", (v & TODA_FAULT_WINO) ? "wino_fwd_ws_kernel" : "");
+    toda::set_error("device fault word 0x%x: a bounded inter-workgroup wait gave up (%s%s%s); the results of that launch are invalid",
+                    v, (v & TODA_FAULT_BN2D) ? "bn2d split kernel " : "", (v & TODA_FAULT_WINO) ? "wino_fwd_ws_kernel " : "",
+                    (v & TODA_FAULT_FPS) ? "fps_multi_kernel" : "");
     return TODA_EFAULT;
 }

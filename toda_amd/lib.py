@@ -105,6 +105,18 @@ SIGNATURES = {
     "toda_voxel_pool_bwd_feat": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "toda_voxel_pool_bwd_pos_doubles": (_sz, [_i]),
     "toda_voxel_pool_bwd_pos": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "toda_fps_resident_blocks": (_i, []),
+    "toda_fps_workspace_bytes": (_sz, [_i, _i]),
+    "toda_fps": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "toda_ball_query_stack": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "toda_sa_gather_fwd": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "toda_sa_gather_bwd_feat": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    "toda_sa_gather_bwd_pos_doubles": (_sz, [_i]),
+    "toda_sa_gather_bwd_pos": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "toda_sa_max_fwd": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "toda_sa_max_bwd": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "toda_bev_interp_fwd": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "toda_bev_interp_bwd": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "toda_clip_adam_chunk": (_i, []),
     "toda_clip_adam_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _i, _vp]),
     "toda_points_in_boxes": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _vp]),

@@ -1961,6 +1961,202 @@ def voxel_neighbor_pool(f, a, b, idx, empty, xyz, new_xyz):
     return _VoxelPool.apply(f, ab, idx.contiguous(), empty.contiguous(), xyz.detach().contiguous(), new_xyz.detach().contiguous())
 
 
+# --------------------------------------------------------------------------- PointNet++ stack layer (PV-RCNN)
+def fps_threads(n):
+    """opt_n_threads of the reference's sampling_gpu.cu:9-13 (its double arithmetic): the thread stride whose residues break ties."""
+    import math
+    return max(min(1 << int(math.log(float(n)) / math.log(2.0)), 1024), 1)
+
+
+def farthest_point_sample(xyz, counts, npoint, mode=0):
+    """Farthest point sampling of every sample of a stacked cloud (reference pointnet2_stack/src/sampling_gpu.cu:25-140, one
+    call per sample there): xyz [N, 3] fp32, counts = per-sample point counts (python ints).  Returns [B, npoint] int32 sample-local
+    indices, index for index the reference kernel's.  mode 0 picks the kernel by sample size, 1 = one workgroup per sample (the
+    reference's algorithm), 2 = co-resident workgroup groups."""
+    lib = L.load()
+    v = xyz.detach().contiguous()
+    if v.dtype != torch.float32 or v.dim() != 2 or v.shape[1] != 3:
+        raise RuntimeError("farthest_point_sample: xyz [N, 3] fp32")
+    counts = [int(c) for c in counts]
+    starts = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    if starts[-1] != v.shape[0]:
+        raise RuntimeError(f"farthest_point_sample: counts sum to {starts[-1]}, xyz has {v.shape[0]} rows")
+    b = len(counts)
+    idx = torch.empty((b, int(npoint)), dtype=torch.int32, device=v.device)
+    temp = torch.empty((max(v.shape[0], 1),), dtype=torch.float32, device=v.device)
+    nbytes = lib.toda_fps_workspace_bytes(min(b, 16), int(npoint))
+    ws = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=v.device)
+    st = L.host_i32(starts.tolist())
+    rc = lib.toda_fps(L.ptr(v) if v.shape[0] else None, L.hptr(st), b, int(npoint), int(mode), L.ptr(temp), L.ptr(idx), L.ptr(ws), nbytes,
+                      L.stream())
+    L.check(rc, "toda_fps")
+    return idx
+
+
+def batch_starts(counts, device):
+    """[B + 1] int32 device offsets of a batch-contiguous stack from its per-sample counts (python ints or a device tensor)."""
+    c = counts if torch.is_tensor(counts) else torch.tensor([int(x) for x in counts], dtype=torch.int32)
+    c = c.to(device=device, dtype=torch.int32)
+    return torch.cat([c.new_zeros(1), torch.cumsum(c, 0, dtype=torch.int32)])
+
+
+def ball_query_stack(radii, nsamples, xyz, xyz_start, new_xyz, new_start):
+    """The stacked ball query (reference src/ball_query_gpu.cu:15-64 + BallQuery.forward) for several radii in one scan:
+    xyz [N, 3] / new_xyz [M, 3] batch-contiguous, xyz_start / new_start [B + 1] int32 device offsets (batch_starts).  Returns one
+    (idx [M, ns] int32, empty [M] bool) per radius; idx holds rows of xyz (the reference's sample-local index plus the sample's
+    first row), zeros for an empty ball."""
+    lib = L.load()
+    v = xyz.detach().contiguous()
+    nx = new_xyz.detach().contiguous()
+    if v.dtype != torch.float32 or nx.dtype != torch.float32 or v.dim() != 2 or v.shape[1] != 3 or nx.dim() != 2 or nx.shape[1] != 3:
+        raise RuntimeError("ball_query_stack: xyz [N, 3], new_xyz [M, 3] fp32")
+    m, n = nx.shape[0], v.shape[0]
+    outs = [(torch.empty((m, int(ns)), dtype=torch.int32, device=nx.device), torch.empty((m,), dtype=torch.bool, device=nx.device))
+            for ns in nsamples]
+    rad = L.host_f32(radii)
+    nsh = L.host_i32(nsamples)
+    ip = L.host_ptrs([o[0] for o in outs])
+    ep = L.host_ptrs([o[1] for o in outs])
+    xs = xyz_start.contiguous()
+    ns_ = new_start.contiguous()
+    rc = lib.toda_ball_query_stack(L.ptr(v) if n else None, n, L.ptr(xs), L.ptr(nx), L.ptr(ns_), xs.shape[0] - 1, m, len(outs), L.hptr(rad),
+                                   L.hptr(nsh), ip, ep, L.stream())
+    L.check(rc, "toda_ball_query_stack")
+    return outs
+
+
+def _neighbour_table(idx, empty, n):
+    """Inverse table of idx [M, ns] over n rows (toda_voxel_pool_table): off [n + 1], ent [M ns] entries per row, ascending."""
+    lib = L.load()
+    m, ns = idx.shape
+    off = torch.empty((n + 1,), dtype=torch.int32, device=idx.device)
+    ent = torch.empty((max(m * ns, 1),), dtype=torch.int32, device=idx.device)
+    nbytes = lib.toda_voxel_pool_table_bytes(m, ns, n)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=idx.device)
+    rc = lib.toda_voxel_pool_table(L.ptr(idx), L.ptr(empty), m, ns, n, L.ptr(off), L.ptr(ent), L.ptr(ws), nbytes, L.stream())
+    L.check(rc, "toda_voxel_pool_table")
+    return off, ent
+
+
+class _SAGather(torch.autograd.Function):
+    """z [M ns, C] = P[idx] + wd . (xyz[idx] - new_xyz), 0 for empty balls: layer 1 of StackSAModuleMSG's MLP on the grouped
+    [relative xyz, features] (reference QueryAndGroup + Conv2d 1 x 1), its feature part projected per source row beforehand."""
+
+    @staticmethod
+    def forward(ctx, P, wd, idx, empty, xyz, new_xyz):
+        lib = L.load()
+        P = P.contiguous()
+        wd = wd.contiguous()
+        n, c = P.shape
+        m, ns = idx.shape
+        z = torch.empty((m * ns, c), dtype=torch.float32, device=P.device)
+        rc = lib.toda_sa_gather_fwd(L.ptr(P) if n else None, n, c, L.ptr(wd), L.ptr(idx), L.ptr(empty), m, ns, L.ptr(xyz) if n else None,
+                                    L.ptr(new_xyz), L.ptr(z), L.stream())
+        L.check(rc, "toda_sa_gather_fwd")
+        ctx.save_for_backward(idx, empty, xyz, new_xyz)
+        ctx.meta = (n, c)
+        return z
+
+    @staticmethod
+    def backward(ctx, gz):
+        lib = L.load()
+        idx, empty, xyz, new_xyz = ctx.saved_tensors
+        n, c = ctx.meta
+        m, ns = idx.shape
+        gz = gz.contiguous()
+        gP = gwd = None
+        if ctx.needs_input_grad[0]:
+            off, ent = _neighbour_table(idx, empty, n)
+            gP = torch.empty((n, c), dtype=torch.float32, device=gz.device)
+            rc = lib.toda_sa_gather_bwd_feat(L.ptr(gz), m, ns, c, L.ptr(off), L.ptr(ent), n, L.ptr(gP), L.stream())
+            L.check(rc, "toda_sa_gather_bwd_feat")
+        if ctx.needs_input_grad[1]:
+            ws = torch.empty((lib.toda_sa_gather_bwd_pos_doubles(c),), dtype=torch.float64, device=gz.device)
+            gwd = torch.empty((c, 3), dtype=torch.float32, device=gz.device)
+            rc = lib.toda_sa_gather_bwd_pos(L.ptr(gz), L.ptr(idx), L.ptr(empty), m, ns, c, L.ptr(xyz) if n else None, n, L.ptr(new_xyz),
+                                            L.ptr(ws), L.ptr(gwd), L.stream())
+            L.check(rc, "toda_sa_gather_bwd_pos")
+        return gP, gwd, None, None, None, None
+
+
+def sa_gather(P, wd, idx, empty, xyz, new_xyz):
+    if P.dtype != torch.float32 or P.dim() != 2 or wd.shape != (P.shape[1], 3) or idx.dim() != 2:
+        raise RuntimeError("sa_gather: P [N, C] fp32, wd [C, 3], idx [M, nsample]")
+    return _SAGather.apply(P, wd.float(), idx.contiguous(), empty.contiguous(), xyz.detach().contiguous(), new_xyz.detach().contiguous())
+
+
+class _SAMax(torch.autograd.Function):
+    """[M ns, C] -> [M, C]: F.max_pool2d over nsample (reference pointnet2_modules.py:106-109); the gradient goes to the first
+    arg-max (none where the maximum is 0: the ReLU before it passes nothing there)."""
+
+    @staticmethod
+    def forward(ctx, y, m, ns):
+        lib = L.load()
+        y = y.contiguous()
+        c = y.shape[1]
+        out = torch.empty((m, c), dtype=torch.float32, device=y.device)
+        arg = torch.empty((m, c), dtype=torch.uint8, device=y.device)
+        L.check(lib.toda_sa_max_fwd(L.ptr(y), m, ns, c, L.ptr(out), L.ptr(arg), L.stream()), "toda_sa_max_fwd")
+        ctx.save_for_backward(arg)
+        ctx.meta = (m, ns, c)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (arg,) = ctx.saved_tensors
+        m, ns, c = ctx.meta
+        gy = torch.empty((m * ns, c), dtype=torch.float32, device=g.device)
+        L.check(L.load().toda_sa_max_bwd(L.ptr(g.contiguous()), L.ptr(arg), m, ns, c, L.ptr(gy), L.stream()), "toda_sa_max_bwd")
+        return gy, None, None
+
+
+def sa_max(y, m, ns):
+    if y.dtype != torch.float32 or y.dim() != 2 or y.shape[0] != m * ns:
+        raise RuntimeError("sa_max: y [M x nsample, C] fp32")
+    return _SAMax.apply(y, int(m), int(ns))
+
+
+class _BevInterp(torch.autograd.Function):
+    """bilinear_interpolate_torch of the reference (voxel_set_abstraction.py:11-42) per keypoint of its sample, read from the
+    [B, C, H, W] map in place; backward through the pixel-sorted tap table."""
+
+    @staticmethod
+    def forward(ctx, fmap, xy, bidx):
+        lib = L.load()
+        fmap = fmap.contiguous()
+        b, c, h, w = fmap.shape
+        k = xy.shape[0]
+        out = torch.empty((k, c), dtype=torch.float32, device=fmap.device)
+        need = ctx.needs_input_grad[0]
+        taps = torch.empty((k, 4), dtype=torch.int32, device=fmap.device) if need else None
+        wts = torch.empty((k, 4), dtype=torch.float32, device=fmap.device) if need else None
+        rc = lib.toda_bev_interp_fwd(L.ptr(fmap), b, c, h, w, L.ptr(xy), L.ptr(bidx), k, L.ptr(out), L.ptr(taps), L.ptr(wts), L.stream())
+        L.check(rc, "toda_bev_interp_fwd")
+        if need:
+            ctx.save_for_backward(taps, wts)
+        ctx.meta = (b, c, h, w)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        taps, wts = ctx.saved_tensors
+        b, c, h, w = ctx.meta
+        k = taps.shape[0]
+        off, ent = _neighbour_table(taps, torch.zeros((k,), dtype=torch.bool, device=g.device), b * h * w)
+        gmap = torch.empty((b, c, h, w), dtype=torch.float32, device=g.device)
+        rc = L.load().toda_bev_interp_bwd(L.ptr(g.contiguous()), k, c, L.ptr(off), L.ptr(ent), L.ptr(wts), b, h, w, L.ptr(gmap), L.stream())
+        L.check(rc, "toda_bev_interp_bwd")
+        return gmap, None, None
+
+
+def bev_interpolate(fmap, x, y, bidx):
+    """[K, C] features of the BEV map fmap [B, C, H, W] at the fractional (column x, row y) [K] of sample bidx [K]."""
+    if fmap.dtype != torch.float32 or fmap.dim() != 4:
+        raise RuntimeError("bev_interpolate: fmap [B, C, H, W] fp32")
+    xy = torch.stack([x.detach().float(), y.detach().float()], dim=1).contiguous()
+    return _BevInterp.apply(fmap, xy, bidx.to(torch.int32).contiguous())
+
+
 # --------------------------------------------------------------------------- point tables (mix processors, range mask)
 def _rows(points, n_dev):
     if points.dtype != torch.float32 or points.dim() != 2:

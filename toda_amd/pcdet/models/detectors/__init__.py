@@ -2,6 +2,7 @@ from .centerpoint import CenterPoint
 from .detector3d_template import Detector3DTemplate
 from .second_net import PointPillar, SECONDNet
 from .second_net_iou import SECONDNetIoU
+from .pv_rcnn import PVRCNN
 from .voxel_rcnn import VoxelRCNN
 
 __all__ = {
@@ -11,6 +12,7 @@ __all__ = {
     "CenterPoint": CenterPoint,
     "SECONDNetIoU": SECONDNetIoU,
     "VoxelRCNN": VoxelRCNN,
+    "PVRCNN": PVRCNN,
 }
 
 
