@@ -450,7 +450,8 @@ int toda_roi_iou3d_max(const float* rois, int B, int N, int roi_stride, const in
  * toda_voxel_pool_fwd: out[m, c] = max_s relu(f[idx[m, s], c] [not empty] + ab[c, 0:3] . d_ms + ab[c, 3]); f [N, C], ab [C, 4],
  * out [M, C]; arg [M, C] uint8 (NULL: not stored) = first arg-max s, 0xff where out is 0.
  * toda_voxel_pool_table: the inverse neighbour table of idx: off [N + 1] (exclusive prefix of the per-row counts), ent [M x
- * nsample] = entries m * nsample + s of row n at ent[off[n] .. off[n + 1]), ascending; empty balls are left out.
+ * nsample] = entries m * nsample + s of row n at ent[off[n] .. off[n + 1]), ascending; empty balls are left out; any nsample with
+ * M x nsample < 2^31.
  * toda_voxel_pool_bwd_feat: gf [N, C] = d out / d f through the table; toda_voxel_pool_bwd_pos: gab [C, 4] = d out / d ab,
  * ws [toda_voxel_pool_bwd_pos_doubles(C)] doubles.  Integer atomics only: every result is bit-reproducible.
  * ---------------------------------------------------------------------- */
@@ -486,8 +487,8 @@ int toda_voxel_pool_bwd_pos(const float* gout, const uint8_t* arg, const int32_t
  * toda_sa_gather_fwd: layer 1 of a StackSAModuleMSG MLP after its feature GEMM: z [M x nsample, C] = P[idx] + wd [C, 3] . d,
  * d = xyz[idx] - new_xyz, 0 for an empty ball.  Backward: gP [N, C] through the inverse neighbour table of
  * toda_voxel_pool_table (toda_sa_gather_bwd_feat), gwd [C, 3] from fp64 partials (ws [toda_sa_gather_bwd_pos_doubles(C)]).
- * toda_sa_max_fwd: out [M, C] = max over nsample of y [M x nsample, C], arg [M, C] uint8 the first arg-max (0xff where the
- * maximum is 0); toda_sa_max_bwd: gy [M x nsample, C].
+ * toda_sa_max_fwd: out [M, C] = max over nsample (<= 254) of y [M x nsample, C], arg [M, C] uint8 the first arg-max, whatever
+ * the sign of the maximum (F.max_pool2d's gradient); toda_sa_max_bwd: gy [M x nsample, C].
  * toda_bev_interp_fwd: voxel_set_abstraction.py's bilinear_interpolate_torch from map [B, C, H, W] at xy [K, 2] (column, row)
  * of sample bidx [K]: out [K, C]; taps [K, 4] pixel ids (b H + y) W + x of Ia Ib Ic Id and wts [K, 4] their weights (both NULL:
  * not stored).  toda_bev_interp_bwd: gmap [B, C, H, W] through the pixel table of taps (toda_voxel_pool_table with

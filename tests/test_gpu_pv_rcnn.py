@@ -64,6 +64,9 @@ def ball_query_restated(radius, nsample, xyz, xs, new_xyz, ns_):
     r2 = torch.tensor(radius, dtype=torch.float32) * torch.tensor(radius, dtype=torch.float32)
     for b in range(len(xs) - 1):
         pts = xyz[xs[b]:xs[b + 1]]
+        if pts.shape[0] == 0:                                 # a sample without points: every ball of its queries is empty
+            empty[ns_[b]:ns_[b + 1]] = True
+            continue
         for q0 in range(ns_[b], ns_[b + 1], 512):
             q1 = min(q0 + 512, ns_[b + 1])
             c = new_xyz[q0:q1]

@@ -118,12 +118,12 @@ def test_voxel_query_at_waymo_training_shape():
     assert bool((~empty).any()) and bool(empty.any())
 
 
-def pool_inputs(seed, n=4000, m=2500, c=32, nsample=16, gamma_pos=0.02, spacing=0.5):
+def pool_inputs(seed, n=4000, m=2500, c=32, nsample=16, gamma_pos=0.02, spacing=0.5, radius=0.6):
     """A level, its query and features whose pooled maxima beat every other voxel's value by far more than fp32 rounding:
     per channel the rows carry distinct multiples of `spacing` (+ spacing / 2), while the position term (BatchNorm2d scale
     gamma_pos, so about 4 gamma_pos at most) varies by well under spacing / 2."""
     shape = [10, 80, 64]
-    (idx, empty), _, _ = query_case(2, shape, n, m // 2, 2, 0.6, (2, 3, 3), nsample, seed, "rowof")
+    (idx, empty), _, _ = query_case(2, shape, n, m // 2, 2, radius, (2, 3, 3), nsample, seed, "rowof")
     coords = make_level(2, shape, n, seed, "sorted")
     xyz = get_voxel_centers(coords[:, 1:4], 2, VSIZE, PC_RANGE).contiguous()
     lo = [PC_RANGE[j] - 1.0 for j in range(3)]

@@ -35,7 +35,7 @@ constexpr int BQ_BLOCK = 256;
 constexpr int BQ_MAX_R = 4;
 constexpr int BQ_MAX_NSAMPLE = 128;
 constexpr int SA_BLOCK = 256;
-constexpr int SA_ARG_NONE = 0xff;
+constexpr int SA_MAX_NSAMPLE = 254;          // sa_max keeps its arg-max in a byte
 constexpr int SB_LANES = 4;
 constexpr int SB_BLOCKS = 256;
 
@@ -340,7 +340,8 @@ sa_gather_bwd_pos_fold_kernel(const double* __restrict__ part, int nblk, int C, 
     gwd[i] = (float)acc;
 }
 
-// out[m, c] = max_s y[m, s, c], arg = first arg-max s, 0xff where the maximum is 0 (y >= 0 after the ReLU: no gradient)
+// out[m, c] = max_s y[m, s, c], arg = first arg-max s whatever its sign (F.max_pool2d's gradient; the ReLU before it is an op of
+// its own and masks its zeros in its own backward)
 __global__ void __launch_bounds__(SA_BLOCK)
 sa_max_fwd_kernel(const float* __restrict__ y, int M, int ns, int C, float* __restrict__ out, uint8_t* __restrict__ arg) {
     const long long i = (long long)blockIdx.x * SA_BLOCK + threadIdx.x;
@@ -358,7 +359,7 @@ sa_max_fwd_kernel(const float* __restrict__ y, int M, int ns, int C, float* __re
         }
     }
     out[i] = best;
-    if (arg) arg[i] = best > 0.0f ? (uint8_t)at : (uint8_t)SA_ARG_NONE;
+    if (arg) arg[i] = (uint8_t)at;
 }
 
 __global__ void __launch_bounds__(SA_BLOCK)
@@ -459,7 +460,7 @@ static int fps_resident_blocks() {
 
 static int sa_check(const char* what, long long M, int ns, int N, int C) {
     TODA_CHECK_ARG(M >= 0 && N >= 0, "%s: negative sizes", what);
-    TODA_CHECK_ARG(ns >= 1 && ns <= SA_ARG_NONE - 1, "%s: nsample %d outside [1, %d]", what, ns, SA_ARG_NONE - 1);
+    TODA_CHECK_ARG(ns >= 1 && ns <= SA_MAX_NSAMPLE, "%s: nsample %d outside [1, %d]", what, ns, SA_MAX_NSAMPLE);
     TODA_CHECK_ARG(C >= 1 && C <= 4096, "%s: channels %d outside [1, 4096]", what, C);
     // the 1-D launches take cdiv(elements, 256) workgroups as an int: keep every element count below 2^38
     TODA_CHECK_ARG(M * ns < (1LL << 31) && M * ns * C < (1LL << 38) && (long long)N * C < (1LL << 38), "%s: too many entries", what);

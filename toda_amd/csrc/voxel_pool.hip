@@ -361,8 +361,9 @@ extern "C" size_t toda_voxel_pool_table_bytes(int M, int nsample, int N) {
 
 extern "C" int toda_voxel_pool_table(const int32_t* idx, const uint8_t* empty, int M, int nsample, int N, int32_t* off, int32_t* ent,
                                      void* ws, size_t ws_bytes, void* stream) {
-    int rc = vp_check_sizes("voxel_pool_table", M, nsample, N, 1);
-    if (rc) return rc;
+    // not bounded by VP_MAX_NSAMPLE: the SA gather (nsample <= 254) and the BEV taps (4) build their tables here too
+    TODA_CHECK_ARG(M >= 0 && N >= 0 && nsample >= 1 && (long long)M * nsample < (1LL << 31), "voxel_pool_table: M=%d nsample=%d N=%d",
+                   M, nsample, N);
     TODA_CHECK_ARG(off && ws && (M == 0 || (idx && empty && ent)), "voxel_pool_table: null pointer");
     const VtLayout L = vt_layout(M, nsample, N);
     if (ws_bytes < L.bytes) {
@@ -378,7 +379,7 @@ extern "C" int toda_voxel_pool_table(const int32_t* idx, const uint8_t* empty, i
     hipLaunchKernelGGL(voxel_pool_keys_kernel, dim3(cdiv(E, VP_BLOCK)), dim3(VP_BLOCK), 0, s, (const int*)idx, empty, M, nsample, N, ka, va,
                        off);
     TODA_LAUNCH_CHECK();
-    rc = exclusive_scan(PlainAccess{off}, (long long)N + 1, (int32_t*)(w + L.scan_part), nullptr, s);
+    int rc = exclusive_scan(PlainAccess{off}, (long long)N + 1, (int32_t*)(w + L.scan_part), nullptr, s);
     if (rc) return rc;
     int bits = 1;
     while (bits < 31 && (1LL << bits) <= (long long)N) ++bits;          // keys run to N (the empty-ball key)

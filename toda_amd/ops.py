@@ -2087,7 +2087,7 @@ def sa_gather(P, wd, idx, empty, xyz, new_xyz):
 
 class _SAMax(torch.autograd.Function):
     """[M ns, C] -> [M, C]: F.max_pool2d over nsample (reference pointnet2_modules.py:106-109); the gradient goes to the first
-    arg-max (none where the maximum is 0: the ReLU before it passes nothing there)."""
+    arg-max whatever its sign, as F.max_pool2d's does."""
 
     @staticmethod
     def forward(ctx, y, m, ns):
