@@ -964,23 +964,26 @@ static inline bool pg_small(long long r1, long long r2, int gz) { return gz == 1
 // matrix path "split" (toda_set_matrix_path): the same accessors and stores around pg_tile_split - 128 x 128 tiles, one 512-thread
 // workgroup per CU.  Also for the grids that fill the 256 CUs badly at that tile size (278 tiles: the stride-2 forward 149 us against 157
 // on the fp32 form, the 2 x 2 deblock's data gradient 125 against 129); 128 x 64 tiles for those measured slower (156 / 132).
-static inline bool pg_split_grid(long long r1, long long r2, int gz) {
-    if (toda_matrix_path() != 1) return false;
+// Contractions shorter than one stage (kc < PG_K: a deblock fed by 3 channels, a stride-2 layer producing fewer than 32) stay on the fp32
+// kernels, as the sparse gather-GEMMs do below 32 channels: with a handful of products per output the dropped cross terms of the split
+// are no longer small against fp32's own rounding (a 3-channel deblock forward measured 1.9-2.1 x the fp32 kernel's rms error).
+static inline bool pg_split_grid(long long r1, long long r2, int gz, long long kc) {
+    if (toda_matrix_path() != 1 || kc < PG_K) return false;
     static const int env = getenv("TODA_PG_SPLIT") ? atoi(getenv("TODA_PG_SPLIT")) : 1;
     (void)r1, (void)r2, (void)gz;
     return env != 0;
 }
-#define PG_LAUNCH(O1, O2, ST, r1, r2, gz, ...)                                                                                             \
+#define PG_LAUNCH(O1, O2, ST, r1, r2, gz, a1, a2, as, kc, ...)                                                                             \
     do {                                                                                                                                   \
-        if (pg_split_grid(r1, r2, gz))                                                                                                      \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(pg_gemm_split_kernel<O1, O2, ST>), dim3(cdiv(r2, 128), cdiv(r1, 128), gz), dim3(PGS_BLOCK), 0,  \
-                               (hipStream_t)stream, __VA_ARGS__);                                                                          \
-        else if (pg_small(r1, r2, gz))                                                                                                       \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(pg_gemm_kernel<64, O1, O2, ST>), dim3(cdiv(r2, 64), cdiv(r1, 64), gz), dim3(PG_BLOCK), 0,    \
-                               (hipStream_t)stream, __VA_ARGS__);                                                                          \
+        if (pg_split_grid(r1, r2, gz, kc))                                                                                                 \
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(pg_gemm_split_kernel<O1, O2, ST>), dim3(cdiv(r2, 128), cdiv(r1, 128), gz), dim3(PGS_BLOCK), 0, \
+                               (hipStream_t)stream, a1, a2, as, kc, __VA_ARGS__);                                                          \
+        else if (pg_small(r1, r2, gz))                                                                                                     \
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(pg_gemm_kernel<64, O1, O2, ST>), dim3(cdiv(r2, 64), cdiv(r1, 64), gz), dim3(PG_BLOCK), 0,   \
+                               (hipStream_t)stream, a1, a2, as, kc, __VA_ARGS__);                                                          \
         else                                                                                                                               \
             hipLaunchKernelGGL(HIP_KERNEL_NAME(pg_gemm_kernel<128, O1, O2, ST>), dim3(cdiv(r2, 128), cdiv(r1, 128), gz), dim3(PG_BLOCK), 0, \
-                               (hipStream_t)stream, __VA_ARGS__);                                                                          \
+                               (hipStream_t)stream, a1, a2, as, kc, __VA_ARGS__);                                                          \
     } while (0)
 
 static int pg_check(const char* who, int B, int Cin, int Cout, int H, int W) {
@@ -1017,7 +1020,7 @@ extern "C" int toda_conv3x3s2_dgrad(const float* dy, const float* w, int batch, 
     WS2Dgrad o1{w, cin, cout, S2Class{}};
     PixS2Dgrad o2{dy, batch, cout, H, W, H / 2, W / 2, S2Class{}};
     StoreS2Class st{dx, cin, N, H, W, 0, 0};
-    if (pg_split_grid(cin, N, 4))
+    if (pg_split_grid(cin, N, 4, cout))      // (the one-tap class contracts cout values)
         hipLaunchKernelGGL(pg_s2_dgrad_split_kernel, dim3(cdiv(N, 128), cdiv(cin, 128), 4), dim3(PGS_BLOCK), 0, (hipStream_t)stream, o1, o2, st);
     else if ((long long)cdiv(cin, 128) * cdiv(N, 128) * 4 < 768)
         hipLaunchKernelGGL(pg_s2_dgrad_kernel<64>, dim3(cdiv(N, 64), cdiv(cin, 64), 4), dim3(PG_BLOCK), 0, (hipStream_t)stream, o1, o2, st);
