@@ -449,9 +449,10 @@ int toda_roi_iou3d_max(const float* rois, int B, int N, int roi_stride, const in
  * M x nsample entries, fp64, fixed-order; ws [toda_voxel_pool_moments_doubles()] doubles, the result in ws[0:12].
  * toda_voxel_pool_fwd: out[m, c] = max_s relu(f[idx[m, s], c] [not empty] + ab[c, 0:3] . d_ms + ab[c, 3]); f [N, C], ab [C, 4],
  * out [M, C]; arg [M, C] uint8 (NULL: not stored) = first arg-max s, 0xff where out is 0.
- * toda_voxel_pool_table: the inverse neighbour table of idx: off [N + 1] (exclusive prefix of the per-row counts), ent [M x
- * nsample] = entries m * nsample + s of row n at ent[off[n] .. off[n + 1]), ascending; empty balls are left out; any nsample with
- * M x nsample < 2^31.
+ * toda_voxel_pool_table: the inverse neighbour table of any idx [M, nsample] over N rows (the name is kept for ABI stability):
+ * off [N + 1] (exclusive prefix of the per-row counts), ent [M x nsample] = entries m * nsample + s of row n at
+ * ent[off[n] .. off[n + 1]), ascending; empty balls are left out; any nsample with M x nsample < 2^31.  Three consumers:
+ * toda_voxel_pool_bwd_feat, toda_sa_gather_bwd_feat and toda_bev_interp_bwd (the last two below).
  * toda_voxel_pool_bwd_feat: gf [N, C] = d out / d f through the table; toda_voxel_pool_bwd_pos: gab [C, 4] = d out / d ab,
  * ws [toda_voxel_pool_bwd_pos_doubles(C)] doubles.  Integer atomics only: every result is bit-reproducible.
  * ---------------------------------------------------------------------- */

@@ -209,14 +209,14 @@ dv_pillar_decorate_kernel(const float* __restrict__ pts, const int32_t* __restri
 
 // ---- workspace ---------------------------------------------------------------------------------------------------------------
 struct DvLayout {
-    size_t cells, cells_part, keep_pos, keep_part, row_key, ka, va, kb, vb, hist, hist_part, bytes;
+    size_t cells, cells_part, keep_pos, keep_part, row_key, bytes;
+    RsLayout sort;
     long long nwords;
 };
 
 static DvLayout dv_layout(int n, const DvGeom& g) {
     DvLayout L;
     L.nwords = (dv_cells(g) * g.batch + 31) / 32;
-    const int nblk = cdiv(n > 0 ? n : 1, RS_TILE);
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
     L.cells = take((size_t)L.nwords * sizeof(uint2));
@@ -224,13 +224,8 @@ static DvLayout dv_layout(int n, const DvGeom& g) {
     L.keep_pos = take((size_t)(n + 1) * 4);
     L.keep_part = take(scan_partials_bytes(n + 1));
     L.row_key = take((size_t)n * 8);
-    L.ka = take((size_t)n * 4);
-    L.va = take((size_t)n * 4);
-    L.kb = take((size_t)n * 4);
-    L.vb = take((size_t)n * 4);
-    L.hist = take((size_t)RS_BINS * nblk * 4);
-    L.hist_part = take(scan_partials_bytes((long long)RS_BINS * nblk));
-    L.bytes = o;
+    L.sort = rs_layout(n, o);
+    L.bytes = L.sort.end;
     return L;
 }
 
@@ -305,32 +300,20 @@ extern "C" int toda_dynvox_index(const float* points, int n, int width, int batc
     }
     hipStream_t s = (hipStream_t)stream;
     char* w = (char*)ws;
-    int32_t *ka = (int32_t*)(w + L.ka), *va = (int32_t*)(w + L.va), *kb = (int32_t*)(w + L.kb), *vb = (int32_t*)(w + L.vb);
     long long* row_key = (long long*)(w + L.row_key);
     if (n > 0)
         hipLaunchKernelGGL(dv_rank_kernel, dim3(cdiv(n, DV_BLOCK)), dim3(DV_BLOCK), 0, s, points, n, width, g, (const uint2*)(w + L.cells),
-                           (const int32_t*)(w + L.keep_pos), keep, rows, inv, ka, va, row_key);
+                           (const int32_t*)(w + L.keep_pos), keep, rows, inv, (int32_t*)(w + L.sort.ka), (int32_t*)(w + L.sort.va), row_key);
     TODA_LAUNCH_CHECK();
     if (k == 0) {
         TODA_HIP(hipMemsetAsync(seg_off, 0, 4, s));
         return TODA_OK;
     }
-    int bits = 1;
-    while (bits < 31 && (1LL << bits) < (long long)m) ++bits;
-    const int nblk = cdiv(k, RS_TILE);
-    int32_t* hist = (int32_t*)(w + L.hist);
-    for (int shift = 0; shift < bits; shift += 8) {
-        hipLaunchKernelGGL(rs_hist_kernel, dim3(nblk), dim3(DV_BLOCK), 0, s, ka, k, shift, nblk, hist);
-        TODA_LAUNCH_CHECK();
-        rc = exclusive_scan(PlainAccess{hist}, (long long)RS_BINS * nblk, (int32_t*)(w + L.hist_part), nullptr, s);
-        if (rc) return rc;
-        hipLaunchKernelGGL(rs_scatter_kernel, dim3(nblk), dim3(DV_BLOCK), 0, s, ka, va, k, shift, nblk, hist, kb, vb);
-        TODA_LAUNCH_CHECK();
-        int32_t* t = ka; ka = kb; kb = t;
-        t = va; va = vb; vb = t;
-    }
-    TODA_HIP(hipMemcpyAsync(seg_pts, va, (size_t)k * 4, hipMemcpyDeviceToDevice, s));
-    hipLaunchKernelGGL(dv_heads_kernel, dim3(cdiv(k, DV_BLOCK)), dim3(DV_BLOCK), 0, s, ka, va, row_key, k, m, g, seg_off, coords);
+    const int32_t *skey, *sval;
+    rc = radix_sort_pairs(w, L.sort, k, m, &skey, &sval, s);       // keys = unq_inv in [0, m)
+    if (rc) return rc;
+    TODA_HIP(hipMemcpyAsync(seg_pts, sval, (size_t)k * 4, hipMemcpyDeviceToDevice, s));
+    hipLaunchKernelGGL(dv_heads_kernel, dim3(cdiv(k, DV_BLOCK)), dim3(DV_BLOCK), 0, s, skey, sval, row_key, k, m, g, seg_off, coords);
     hipLaunchKernelGGL(dv_counts_kernel, dim3(cdiv(m, DV_BLOCK)), dim3(DV_BLOCK), 0, s, seg_off, m, cnt);
     TODA_LAUNCH_CHECK();
     return TODA_OK;

@@ -17,12 +17,13 @@
 // Ball query: one lane per query point scans its sample's points in ascending index, tiled through LDS, for up to FPS_MAX_R
 // nested radii at once; d2 < r^2 in the reference's order, the first hit fills the row, later hits slots 1.., stop at nsample.
 // SA pool pieces (the rest of the layer is GEMMs and ops.bn_rows): the gather z1[e] = P[idx[e]] + W_d . d_e of layer 1, the
-// max over nsample with its arg-max, and their backwards through the inverse neighbour table of voxel_pool.hip.
-// BEV bilinear interpolation: the reference's clamped taps and weight formulas; the backward sums each pixel's taps in a
-// pixel-sorted table.  The file is compiled with contraction off; no float atomics: every result is bit-reproducible.
+// max over nsample with its arg-max, and their backwards: d P through the inverse neighbour table (toda_voxel_pool_table, built in
+// voxel_pool.hip for that pool, this gather and the BEV backward), d W_d by the fp64 partials and fold of pool_common.cuh.
+// BEV bilinear interpolation: the reference's clamped taps and weight formulas; the backward sums each pixel's taps in the same
+// table over pixels.  The file is compiled with contraction off; no float atomics: every result is bit-reproducible.
 #include <math.h>
 
-#include "common.h"
+#include "pool_common.cuh"
 
 namespace toda {
 
@@ -260,14 +261,6 @@ ball_query_kernel(const float* __restrict__ xyz, int N, const int* __restrict__ 
     }
 }
 
-// relative position of entry (m, s): xyz[row] - new_xyz[m], zero for an empty ball or a row outside the table
-__device__ __forceinline__ void sa_delta(const float* __restrict__ xyz, const float* __restrict__ new_xyz, int row, int N, int m,
-                                         bool empty, float d[3]) {
-    const bool ok = !empty && (unsigned)row < (unsigned)N;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) d[k] = ok ? xyz[(size_t)row * 3 + k] - new_xyz[(size_t)m * 3 + k] : 0.0f;
-}
-
 // z [E, C], E = M x ns: z[e, c] = P[idx[e], c] + wd[c] . d_e, 0 for an empty ball
 __global__ void __launch_bounds__(SA_BLOCK)
 sa_gather_fwd_kernel(const float* __restrict__ P, int N, int C, const float* __restrict__ wd, const int* __restrict__ idx,
@@ -283,7 +276,7 @@ sa_gather_fwd_kernel(const float* __restrict__ P, int N, int C, const float* __r
     float v = 0.0f;
     if (ok) {
         float d[3];
-        sa_delta(xyz, new_xyz, row, N, m, false, d);
+        rel_delta(xyz, new_xyz, row, N, m, false, d);
         v = P[(size_t)row * C + c] + (wd[c * 3 + 0] * d[0] + wd[c * 3 + 1] * d[1] + wd[c * 3 + 2] * d[2]);
     }
     z[i] = v;
@@ -313,7 +306,7 @@ sa_gather_bwd_pos_kernel(const float* __restrict__ gz, const int* __restrict__ i
             const int m = (int)(e / ns);
             if (empty[m]) continue;
             float d[3];
-            sa_delta(xyz, new_xyz, idx[e], N, m, false, d);
+            rel_delta(xyz, new_xyz, idx[e], N, m, false, d);
             const double g = gz[(size_t)e * C + c];
             v[0] += g * d[0];
             v[1] += g * d[1];
@@ -329,15 +322,6 @@ sa_gather_bwd_pos_kernel(const float* __restrict__ gz, const int* __restrict__ i
             part[((size_t)blockIdx.x * C + c) * 3 + k] = acc;
         }
     }
-}
-
-__global__ void __launch_bounds__(SA_BLOCK)
-sa_gather_bwd_pos_fold_kernel(const double* __restrict__ part, int nblk, int C, float* __restrict__ gwd) {
-    const int i = blockIdx.x * SA_BLOCK + threadIdx.x;
-    if (i >= C * 3) return;
-    double acc = 0.0;
-    for (int b = 0; b < nblk; ++b) acc += part[(size_t)b * C * 3 + i];
-    gwd[i] = (float)acc;
 }
 
 // out[m, c] = max_s y[m, s, c], arg = first arg-max s whatever its sign (F.max_pool2d's gradient; the ReLU before it is an op of
@@ -458,15 +442,6 @@ static int fps_resident_blocks() {
     return blocks;
 }
 
-static int sa_check(const char* what, long long M, int ns, int N, int C) {
-    TODA_CHECK_ARG(M >= 0 && N >= 0, "%s: negative sizes", what);
-    TODA_CHECK_ARG(ns >= 1 && ns <= SA_MAX_NSAMPLE, "%s: nsample %d outside [1, %d]", what, ns, SA_MAX_NSAMPLE);
-    TODA_CHECK_ARG(C >= 1 && C <= 4096, "%s: channels %d outside [1, 4096]", what, C);
-    // the 1-D launches take cdiv(elements, 256) workgroups as an int: keep every element count below 2^38
-    TODA_CHECK_ARG(M * ns < (1LL << 31) && M * ns * C < (1LL << 38) && (long long)N * C < (1LL << 38), "%s: too many entries", what);
-    return TODA_OK;
-}
-
 }  // namespace toda
 
 using namespace toda;
@@ -572,7 +547,7 @@ extern "C" int toda_ball_query_stack(const float* xyz, int N, const int32_t* xyz
 
 extern "C" int toda_sa_gather_fwd(const float* P, int N, int C, const float* wd, const int32_t* idx, const uint8_t* empty, int M, int nsample,
                                   const float* xyz, const float* new_xyz, float* z, void* stream) {
-    int rc = sa_check("sa_gather_fwd", M, nsample, N, C);
+    int rc = pool_check_sizes("sa_gather_fwd", M, nsample, SA_MAX_NSAMPLE, N, C);
     if (rc) return rc;
     if (M == 0) return TODA_OK;
     TODA_CHECK_ARG(wd && idx && empty && new_xyz && z && (N == 0 || (P && xyz)), "sa_gather_fwd: null pointer");
@@ -585,7 +560,7 @@ extern "C" int toda_sa_gather_fwd(const float* P, int N, int C, const float* wd,
 
 extern "C" int toda_sa_gather_bwd_feat(const float* gz, int M, int nsample, int C, const int32_t* off, const int32_t* ent, int N, float* gP,
                                        void* stream) {
-    int rc = sa_check("sa_gather_bwd_feat", M, nsample, N, C);
+    int rc = pool_check_sizes("sa_gather_bwd_feat", M, nsample, SA_MAX_NSAMPLE, N, C);
     if (rc) return rc;
     if (N == 0) return TODA_OK;
     TODA_CHECK_ARG(off && gP && (M == 0 || (gz && ent)), "sa_gather_bwd_feat: null pointer");
@@ -599,19 +574,19 @@ extern "C" size_t toda_sa_gather_bwd_pos_doubles(int C) { return C < 1 ? 0 : (si
 
 extern "C" int toda_sa_gather_bwd_pos(const float* gz, const int32_t* idx, const uint8_t* empty, int M, int nsample, int C, const float* xyz,
                                       int N, const float* new_xyz, double* ws, float* gwd, void* stream) {
-    int rc = sa_check("sa_gather_bwd_pos", M, nsample, N, C);
+    int rc = pool_check_sizes("sa_gather_bwd_pos", M, nsample, SA_MAX_NSAMPLE, N, C);
     if (rc) return rc;
     TODA_CHECK_ARG(ws && gwd && (M == 0 || (gz && idx && empty && new_xyz)) && (N == 0 || xyz), "sa_gather_bwd_pos: null pointer");
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(sa_gather_bwd_pos_kernel, dim3(SB_BLOCKS, cdiv(C, 64)), dim3(SA_BLOCK), 0, s, gz, (const int*)idx, empty, nsample,
                        (long long)M * nsample, C, xyz, N, new_xyz, ws);
-    hipLaunchKernelGGL(sa_gather_bwd_pos_fold_kernel, dim3(cdiv(C * 3, SA_BLOCK)), dim3(SA_BLOCK), 0, s, (const double*)ws, SB_BLOCKS, C, gwd);
+    hipLaunchKernelGGL(pool_fold_partials_kernel, dim3(cdiv(C * 3, FOLD_BLOCK)), dim3(FOLD_BLOCK), 0, s, (const double*)ws, SB_BLOCKS, C * 3, gwd);
     TODA_LAUNCH_CHECK();
     return TODA_OK;
 }
 
 extern "C" int toda_sa_max_fwd(const float* y, int M, int nsample, int C, float* out, uint8_t* arg, void* stream) {
-    int rc = sa_check("sa_max_fwd", M, nsample, 0, C);
+    int rc = pool_check_sizes("sa_max_fwd", M, nsample, SA_MAX_NSAMPLE, 0, C);
     if (rc) return rc;
     if (M == 0) return TODA_OK;
     TODA_CHECK_ARG(y && out, "sa_max_fwd: null pointer");
@@ -622,7 +597,7 @@ extern "C" int toda_sa_max_fwd(const float* y, int M, int nsample, int C, float*
 }
 
 extern "C" int toda_sa_max_bwd(const float* g, const uint8_t* arg, int M, int nsample, int C, float* gy, void* stream) {
-    int rc = sa_check("sa_max_bwd", M, nsample, 0, C);
+    int rc = pool_check_sizes("sa_max_bwd", M, nsample, SA_MAX_NSAMPLE, 0, C);
     if (rc) return rc;
     if (M == 0) return TODA_OK;
     TODA_CHECK_ARG(g && arg && gy, "sa_max_bwd: null pointer");

@@ -1,7 +1,7 @@
 // Stable LSD radix sort of (int32 key, int32 val) pairs, 8 bits per pass: per-workgroup digit histograms (rs_hist), a device
-// scan over them in digit-major order (scan.cuh), then a scatter that ranks equal digits in input order (rs_scatter).  Shared by
-// the dynamic voxel index (dynvox.hip) and the inverse neighbour table of the voxel pool (voxel_pool.hip).  The kernels are
-// static: every translation unit that includes this header compiles and registers its own copy.  Integer atomics on LDS only.
+// scan over them in digit-major order (scan.cuh), then a scatter that ranks equal digits in input order (rs_scatter); the host
+// driver radix_sort_pairs runs the passes.  Two users: the dynamic voxel index (dynvox.hip) and the inverse neighbour table
+// (voxel_pool.hip).  The kernels are static: every translation unit that includes this header has its own copy.  LDS integer atomics only.
 #pragma once
 #include "scan.cuh"
 
@@ -71,6 +71,52 @@ rs_scatter_kernel(const int32_t* __restrict__ key_in, const int32_t* __restrict_
         s_base[t] += add;
         __syncthreads();
     }
+}
+
+// workspace of one sort of up to n pairs, from byte `base` of the caller's buffer: the two ping-pong (key, val) pairs, the
+// digit-major histogram and its scan partials, 256-byte aligned slots; `end` = the first byte after them
+struct RsLayout {
+    size_t ka, va, kb, vb, hist, hist_part, end;
+};
+
+static RsLayout rs_layout(long long n, size_t base) {
+    RsLayout L;
+    const int nblk = cdiv(n > 0 ? n : 1, RS_TILE);
+    size_t o = base;
+    auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
+    L.ka = take((size_t)n * 4);
+    L.va = take((size_t)n * 4);
+    L.kb = take((size_t)n * 4);
+    L.vb = take((size_t)n * 4);
+    L.hist = take((size_t)RS_BINS * nblk * 4);
+    L.hist_part = take(scan_partials_bytes((long long)RS_BINS * nblk));
+    L.end = o;
+    return L;
+}
+
+// sorts the n pairs the caller wrote to (ka, va) of `ws` by key, keys in [0, bound): one hist -> scan -> scatter pass per 8 bits
+// of bound - 1, ping-pong between the two pairs.  *keys / *vals (either may be NULL) = the pair that holds the result.
+static int radix_sort_pairs(void* ws, const RsLayout& L, int n, long long bound, const int32_t** keys, const int32_t** vals,
+                            hipStream_t s) {
+    char* w = (char*)ws;
+    int32_t *ka = (int32_t*)(w + L.ka), *va = (int32_t*)(w + L.va), *kb = (int32_t*)(w + L.kb), *vb = (int32_t*)(w + L.vb);
+    int32_t* hist = (int32_t*)(w + L.hist);
+    int bits = 1;
+    while (bits < 31 && (1LL << bits) < bound) ++bits;
+    const int nblk = cdiv(n, RS_TILE);
+    for (int shift = 0; n > 0 && shift < bits; shift += 8) {
+        hipLaunchKernelGGL(rs_hist_kernel, dim3(nblk), dim3(RS_BLOCK), 0, s, ka, n, shift, nblk, hist);
+        TODA_LAUNCH_CHECK();
+        int rc = exclusive_scan(PlainAccess{hist}, (long long)RS_BINS * nblk, (int32_t*)(w + L.hist_part), nullptr, s);
+        if (rc) return rc;
+        hipLaunchKernelGGL(rs_scatter_kernel, dim3(nblk), dim3(RS_BLOCK), 0, s, ka, va, n, shift, nblk, hist, kb, vb);
+        TODA_LAUNCH_CHECK();
+        int32_t* t = ka; ka = kb; kb = t;
+        t = va; va = vb; vb = t;
+    }
+    if (keys) *keys = ka;
+    if (vals) *vals = va;
+    return TODA_OK;
 }
 
 }  // namespace toda

@@ -15,9 +15,11 @@
 // (toda_voxel_pool_moments: mean and biased covariance over all M x nsample entries, fp64, fixed-order fold).  The forward then
 // reads every neighbour row once: out[m, c] = max_s relu(f[idx[m, s], c] [not empty] + a_c . d_ms + b_c), with the first
 // arg-max s stored as a byte (0xff where the maximum is 0, i.e. no gradient passes the ReLU).
-// Backward: d f through an inverse neighbour table (per row of the level, its (m, s) entries ascending: integer counts, a scan
-// and the stable radix sort of radix_sort.cuh), one lane per (row, channel) summing its entries in table order; d a, d b as
-// per-workgroup fp64 partials folded in a fixed order.  No float atomics: every result is bit-reproducible.
+// Backward: d f through the inverse neighbour table, one lane per (row, channel) summing its entries in table order; d a, d b as
+// per-workgroup fp64 partials folded in a fixed order (pool_common.cuh).  No float atomics: every result is bit-reproducible.
+// The table (toda_voxel_pool_table, the name kept for ABI stability; per row its (m, s) entries ascending: integer counts, a scan
+// and the stable sort of radix_sort.cuh) also serves the SA gather's d P and the BEV interpolation's d map (pointnet2_stack.hip).
+#include "pool_common.cuh"
 #include "radix_sort.cuh"
 
 namespace toda {
@@ -86,14 +88,6 @@ voxel_query_kernel(const float* __restrict__ new_xyz, const int4* __restrict__ n
     empty[m] = cnt == 0;
 }
 
-// relative position of entry (m, s): voxel centre - grid point, zero for an empty ball or a row outside the level
-__device__ __forceinline__ void vp_delta(const float* __restrict__ xyz, const float* __restrict__ new_xyz, int row, int N, int m,
-                                         bool empty, float d[3]) {
-    const bool ok = !empty && (unsigned)row < (unsigned)N;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) d[k] = ok ? xyz[(size_t)row * 3 + k] - new_xyz[(size_t)m * 3 + k] : 0.0f;
-}
-
 __device__ __forceinline__ void block_sum_doubles(double* v, int nv, double* s_red) {
     // fixed-order tree over the 256 lanes of the block, nv values per lane; result in lane 0's v
     for (int k = 0; k < nv; ++k) s_red[k * VP_BLOCK + threadIdx.x] = v[k];
@@ -116,7 +110,7 @@ voxel_pool_moments_kernel(const int* __restrict__ idx, const uint8_t* __restrict
     for (long long e = (long long)blockIdx.x * VP_BLOCK + threadIdx.x; e < E; e += (long long)gridDim.x * VP_BLOCK) {
         const int m = (int)(e / ns);
         float d[3];
-        vp_delta(xyz, new_xyz, idx[e], N, m, empty[m] != 0, d);
+        rel_delta(xyz, new_xyz, idx[e], N, m, empty[m] != 0, d);
         const double x = d[0], y = d[1], z = d[2];
         v[0] += x; v[1] += y; v[2] += z;
         v[3] += x * x; v[4] += x * y; v[5] += x * z; v[6] += y * y; v[7] += y * z; v[8] += z * z;
@@ -159,7 +153,7 @@ voxel_pool_fwd_kernel(const float* __restrict__ f, int N, int C, const int* __re
         const bool e = empty[m] != 0;
         const int row = idx[(size_t)m * ns + i % ns];
         float d[3];
-        vp_delta(xyz, new_xyz, row, N, m, e, d);
+        rel_delta(xyz, new_xyz, row, N, m, e, d);
         s_row[i] = (!e && (unsigned)row < (unsigned)N) ? row : -1;
         s_d[i * 3 + 0] = d[0];
         s_d[i * 3 + 1] = d[1];
@@ -233,7 +227,7 @@ voxel_pool_bwd_pos_kernel(const float* __restrict__ g, const uint8_t* __restrict
             if (s == VP_ARG_NONE || s >= ns) continue;
             const double gv = g[o];
             float d[3];
-            vp_delta(xyz, new_xyz, idx[(size_t)m * ns + s], N, m, empty[m] != 0, d);
+            rel_delta(xyz, new_xyz, idx[(size_t)m * ns + s], N, m, empty[m] != 0, d);
             v[0] += gv * d[0];
             v[1] += gv * d[1];
             v[2] += gv * d[2];
@@ -251,43 +245,17 @@ voxel_pool_bwd_pos_kernel(const float* __restrict__ g, const uint8_t* __restrict
     }
 }
 
-__global__ void __launch_bounds__(VP_BLOCK)
-voxel_pool_bwd_pos_fold_kernel(const double* __restrict__ part, int nblk, int C, float* __restrict__ gab) {
-    const int i = blockIdx.x * VP_BLOCK + threadIdx.x;
-    if (i >= C * 4) return;
-    double acc = 0.0;
-    for (int b = 0; b < nblk; ++b) acc += part[(size_t)b * C * 4 + i];
-    gab[i] = (float)acc;
-}
-
 struct VtLayout {
-    size_t ka, va, kb, vb, scan_part, hist, hist_part, bytes;
+    RsLayout sort;
+    size_t scan_part, bytes;
 };
 
 static VtLayout vt_layout(int M, int ns, int N) {
     VtLayout l;
-    const long long E = (long long)M * ns;
-    const int nblk = cdiv(E > 0 ? E : 1, RS_TILE);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
-    l.ka = take((size_t)E * 4);
-    l.va = take((size_t)E * 4);
-    l.kb = take((size_t)E * 4);
-    l.vb = take((size_t)E * 4);
-    l.scan_part = take(scan_partials_bytes((long long)N + 1));
-    l.hist = take((size_t)RS_BINS * nblk * 4);
-    l.hist_part = take(scan_partials_bytes((long long)RS_BINS * nblk));
-    l.bytes = o;
+    l.sort = rs_layout((long long)M * ns, 0);
+    l.scan_part = l.sort.end;
+    l.bytes = l.scan_part + scan_partials_bytes((long long)N + 1);
     return l;
-}
-
-static int vp_check_sizes(const char* what, int M, int ns, int N, int C) {
-    TODA_CHECK_ARG(M >= 0 && N >= 0, "%s: negative sizes (M=%d N=%d)", what, M, N);
-    TODA_CHECK_ARG(ns >= 1 && ns <= VP_MAX_NSAMPLE, "%s: nsample %d outside [1, %d]", what, ns, VP_MAX_NSAMPLE);
-    TODA_CHECK_ARG(C >= 1 && C <= 4096, "%s: channels %d outside [1, 4096]", what, C);
-    TODA_CHECK_ARG((long long)M * ns < (1LL << 31) && (long long)M * C < (1LL << 40) && (long long)N * C < (1LL << 40),
-                   "%s: too many entries (M=%d nsample=%d C=%d)", what, M, ns, C);
-    return TODA_OK;
 }
 
 }  // namespace toda
@@ -328,7 +296,7 @@ extern "C" size_t toda_voxel_pool_moments_doubles(void) { return (size_t)VM_BLOC
 
 extern "C" int toda_voxel_pool_moments(const int32_t* idx, const uint8_t* empty, int M, int nsample, const float* xyz, int N,
                                        const float* new_xyz, double* ws, void* stream) {
-    int rc = vp_check_sizes("voxel_pool_moments", M, nsample, N, 1);
+    int rc = pool_check_sizes("voxel_pool_moments", M, nsample, VP_MAX_NSAMPLE, N, 1);
     if (rc) return rc;
     TODA_CHECK_ARG(M >= 1, "voxel_pool_moments: no grid points");
     TODA_CHECK_ARG(idx && empty && new_xyz && ws && (N == 0 || xyz), "voxel_pool_moments: null pointer");
@@ -344,7 +312,7 @@ extern "C" int toda_voxel_pool_moments(const int32_t* idx, const uint8_t* empty,
 
 extern "C" int toda_voxel_pool_fwd(const float* f, int N, int C, const int32_t* idx, const uint8_t* empty, int M, int nsample,
                                    const float* xyz, const float* new_xyz, const float* ab, float* out, uint8_t* arg, void* stream) {
-    int rc = vp_check_sizes("voxel_pool_fwd", M, nsample, N, C);
+    int rc = pool_check_sizes("voxel_pool_fwd", M, nsample, VP_MAX_NSAMPLE, N, C);
     if (rc) return rc;
     if (M == 0) return TODA_OK;
     TODA_CHECK_ARG(idx && empty && new_xyz && ab && out && (N == 0 || (f && xyz)), "voxel_pool_fwd: null pointer");
@@ -375,33 +343,21 @@ extern "C" int toda_voxel_pool_table(const int32_t* idx, const uint8_t* empty, i
     const int E = M * nsample;
     TODA_HIP(hipMemsetAsync(off, 0, (size_t)(N + 1) * 4, s));
     if (E == 0) return TODA_OK;
-    int32_t *ka = (int32_t*)(w + L.ka), *va = (int32_t*)(w + L.va), *kb = (int32_t*)(w + L.kb), *vb = (int32_t*)(w + L.vb);
-    hipLaunchKernelGGL(voxel_pool_keys_kernel, dim3(cdiv(E, VP_BLOCK)), dim3(VP_BLOCK), 0, s, (const int*)idx, empty, M, nsample, N, ka, va,
-                       off);
+    hipLaunchKernelGGL(voxel_pool_keys_kernel, dim3(cdiv(E, VP_BLOCK)), dim3(VP_BLOCK), 0, s, (const int*)idx, empty, M, nsample, N,
+                       (int32_t*)(w + L.sort.ka), (int32_t*)(w + L.sort.va), off);
     TODA_LAUNCH_CHECK();
     int rc = exclusive_scan(PlainAccess{off}, (long long)N + 1, (int32_t*)(w + L.scan_part), nullptr, s);
     if (rc) return rc;
-    int bits = 1;
-    while (bits < 31 && (1LL << bits) <= (long long)N) ++bits;          // keys run to N (the empty-ball key)
-    const int nblk = cdiv(E, RS_TILE);
-    int32_t* hist = (int32_t*)(w + L.hist);
-    for (int shift = 0; shift < bits; shift += 8) {
-        hipLaunchKernelGGL(rs_hist_kernel, dim3(nblk), dim3(RS_BLOCK), 0, s, ka, E, shift, nblk, hist);
-        TODA_LAUNCH_CHECK();
-        rc = exclusive_scan(PlainAccess{hist}, (long long)RS_BINS * nblk, (int32_t*)(w + L.hist_part), nullptr, s);
-        if (rc) return rc;
-        hipLaunchKernelGGL(rs_scatter_kernel, dim3(nblk), dim3(RS_BLOCK), 0, s, ka, va, E, shift, nblk, hist, kb, vb);
-        TODA_LAUNCH_CHECK();
-        int32_t* t = ka; ka = kb; kb = t;
-        t = va; va = vb; vb = t;
-    }
-    TODA_HIP(hipMemcpyAsync(ent, va, (size_t)E * 4, hipMemcpyDeviceToDevice, s));
+    const int32_t* sval;
+    rc = radix_sort_pairs(w, L.sort, E, (long long)N + 1, nullptr, &sval, s);          // keys run to N (the empty-ball key)
+    if (rc) return rc;
+    TODA_HIP(hipMemcpyAsync(ent, sval, (size_t)E * 4, hipMemcpyDeviceToDevice, s));
     return TODA_OK;
 }
 
 extern "C" int toda_voxel_pool_bwd_feat(const float* gout, const uint8_t* arg, int M, int nsample, int C, const int32_t* off,
                                         const int32_t* ent, int N, float* gf, void* stream) {
-    int rc = vp_check_sizes("voxel_pool_bwd_feat", M, nsample, N, C);
+    int rc = pool_check_sizes("voxel_pool_bwd_feat", M, nsample, VP_MAX_NSAMPLE, N, C);
     if (rc) return rc;
     if (N == 0) return TODA_OK;
     TODA_CHECK_ARG(off && gf && (M == 0 || (gout && arg && ent)), "voxel_pool_bwd_feat: null pointer");
@@ -415,14 +371,13 @@ extern "C" size_t toda_voxel_pool_bwd_pos_doubles(int C) { return C < 1 ? 0 : (s
 
 extern "C" int toda_voxel_pool_bwd_pos(const float* gout, const uint8_t* arg, const int32_t* idx, const uint8_t* empty, int M, int nsample,
                                        int C, const float* xyz, int N, const float* new_xyz, double* ws, float* gab, void* stream) {
-    int rc = vp_check_sizes("voxel_pool_bwd_pos", M, nsample, N, C);
+    int rc = pool_check_sizes("voxel_pool_bwd_pos", M, nsample, VP_MAX_NSAMPLE, N, C);
     if (rc) return rc;
     TODA_CHECK_ARG(ws && gab && (M == 0 || (gout && arg && idx && empty && new_xyz)) && (N == 0 || xyz), "voxel_pool_bwd_pos: null pointer");
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(voxel_pool_bwd_pos_kernel, dim3(VB_BLOCKS, cdiv(C, 64)), dim3(VP_BLOCK), 0, s, gout, arg, (const int*)idx, empty, M,
                        nsample, C, xyz, N, new_xyz, ws);
-    hipLaunchKernelGGL(voxel_pool_bwd_pos_fold_kernel, dim3(cdiv(C * 4, VP_BLOCK)), dim3(VP_BLOCK), 0, s, (const double*)ws, VB_BLOCKS, C,
-                       gab);
+    hipLaunchKernelGGL(pool_fold_partials_kernel, dim3(cdiv(C * 4, FOLD_BLOCK)), dim3(FOLD_BLOCK), 0, s, (const double*)ws, VB_BLOCKS, C * 4, gab);
     TODA_LAUNCH_CHECK();
     return TODA_OK;
 }

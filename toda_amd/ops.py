@@ -24,7 +24,6 @@ def grid_size_xyz(pc_range, voxel_size):
 
 # ----------------------------------------------------------------------------- voxelisation
 import os as _os
-import os as _os_early
 import time as _time
 
 _COUNT_PINNED = {}
@@ -1862,6 +1861,25 @@ def roi_iou3d_max(rois, roi_labels, gt_boxes, by_class):
 
 
 # --------------------------------------------------------------------------- voxel query + neighbour pool (VoxelRCNNHead)
+def _ptr_rows(t):
+    """Device pointer of a row table, or NULL when it has no rows."""
+    return L.ptr(t) if t.shape[0] else None
+
+
+def _neighbour_table(idx, empty, n):
+    """Inverse table of idx [M, ns] over n rows (toda_voxel_pool_table): off [n + 1], ent [M ns] entries per row, ascending.
+    Built in the forward of the voxel pool and in the backward of the SA gather and the BEV interpolation."""
+    lib = L.load()
+    m, ns = idx.shape
+    off = torch.empty((n + 1,), dtype=torch.int32, device=idx.device)
+    ent = torch.empty((max(m * ns, 1),), dtype=torch.int32, device=idx.device)
+    nbytes = lib.toda_voxel_pool_table_bytes(m, ns, n)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=idx.device)
+    rc = lib.toda_voxel_pool_table(L.ptr(idx), L.ptr(empty), m, ns, n, L.ptr(off), L.ptr(ent), L.ptr(ws), nbytes, L.stream())
+    L.check(rc, "toda_voxel_pool_table")
+    return off, ent
+
+
 def voxel_query(new_xyz, new_coords, xyz, grid_index, radius, query_range, nsample):
     """The voxel query of one level (reference voxel_query_utils.py:12-44 + src/voxel_query_gpu.cu:10-91): for every grid point
     new_xyz [M, 3] with lattice coordinates new_coords [M, 4] int32 (b, z, y, x), the rows of the level (voxel centres xyz [N, 3])
@@ -1881,7 +1899,7 @@ def voxel_query(new_xyz, new_coords, xyz, grid_index, radius, query_range, nsamp
     empty = torch.empty((m,), dtype=torch.bool, device=nx.device)
     shape_c = L.host_i32(grid_index.shape)
     rng_c = L.host_i32([int(r) for r in query_range])
-    rc = lib.toda_voxel_query(L.ptr(nx), L.ptr(nc), m, L.ptr(v) if n else None, n, L.ptr(grid_index.buf), L.ptr(grid_index.rowof),
+    rc = lib.toda_voxel_query(L.ptr(nx), L.ptr(nc), m, _ptr_rows(v), n, L.ptr(grid_index.buf), L.ptr(grid_index.rowof),
                               grid_index.batch, L.hptr(shape_c), float(radius), L.hptr(rng_c), ns, L.ptr(idx), L.ptr(empty), L.stream())
     L.check(rc, "toda_voxel_query")
     return idx, empty
@@ -1893,7 +1911,7 @@ def voxel_pool_moments(idx, empty, xyz, new_xyz):
     lib = L.load()
     m, ns = idx.shape
     ws = torch.empty((lib.toda_voxel_pool_moments_doubles(),), dtype=torch.float64, device=idx.device)
-    rc = lib.toda_voxel_pool_moments(L.ptr(idx), L.ptr(empty), m, ns, L.ptr(xyz) if xyz.shape[0] else None, xyz.shape[0],
+    rc = lib.toda_voxel_pool_moments(L.ptr(idx), L.ptr(empty), m, ns, _ptr_rows(xyz), xyz.shape[0],
                                      L.ptr(new_xyz), L.ptr(ws), L.stream())
     L.check(rc, "toda_voxel_pool_moments")
     return ws[0:3], ws[3:12].view(3, 3)
@@ -1914,16 +1932,11 @@ class _VoxelPool(torch.autograd.Function):
         need_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         out = torch.empty((m, c), dtype=torch.float32, device=f.device)
         arg = torch.empty((m, c), dtype=torch.uint8, device=f.device) if need_grad else None
-        rc = lib.toda_voxel_pool_fwd(L.ptr(f) if n else None, n, c, L.ptr(idx), L.ptr(empty), m, ns, L.ptr(xyz) if n else None,
+        rc = lib.toda_voxel_pool_fwd(_ptr_rows(f), n, c, L.ptr(idx), L.ptr(empty), m, ns, _ptr_rows(xyz),
                                      L.ptr(new_xyz), L.ptr(ab), L.ptr(out), L.ptr(arg), L.stream())
         L.check(rc, "toda_voxel_pool_fwd")
         if need_grad:
-            off = torch.empty((n + 1,), dtype=torch.int32, device=f.device)
-            ent = torch.empty((max(m * ns, 1),), dtype=torch.int32, device=f.device)
-            nbytes = lib.toda_voxel_pool_table_bytes(m, ns, n)
-            ws = torch.empty((nbytes,), dtype=torch.uint8, device=f.device)
-            rc = lib.toda_voxel_pool_table(L.ptr(idx), L.ptr(empty), m, ns, n, L.ptr(off), L.ptr(ent), L.ptr(ws), nbytes, L.stream())
-            L.check(rc, "toda_voxel_pool_table")
+            off, ent = _neighbour_table(idx, empty, n)
             ctx.save_for_backward(arg, idx, empty, xyz, new_xyz, off, ent)
         ctx.meta = (n, c)
         return out
@@ -1943,7 +1956,7 @@ class _VoxelPool(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             ws = torch.empty((lib.toda_voxel_pool_bwd_pos_doubles(c),), dtype=torch.float64, device=g.device)
             gab = torch.empty((c, 4), dtype=torch.float32, device=g.device)
-            rc = lib.toda_voxel_pool_bwd_pos(L.ptr(g), L.ptr(arg), L.ptr(idx), L.ptr(empty), m, ns, c, L.ptr(xyz) if n else None, n,
+            rc = lib.toda_voxel_pool_bwd_pos(L.ptr(g), L.ptr(arg), L.ptr(idx), L.ptr(empty), m, ns, c, _ptr_rows(xyz), n,
                                              L.ptr(new_xyz), L.ptr(ws), L.ptr(gab), L.stream())
             L.check(rc, "toda_voxel_pool_bwd_pos")
         return gf, gab, None, None, None, None
@@ -2019,23 +2032,10 @@ def ball_query_stack(radii, nsamples, xyz, xyz_start, new_xyz, new_start):
     ep = L.host_ptrs([o[1] for o in outs])
     xs = xyz_start.contiguous()
     ns_ = new_start.contiguous()
-    rc = lib.toda_ball_query_stack(L.ptr(v) if n else None, n, L.ptr(xs), L.ptr(nx), L.ptr(ns_), xs.shape[0] - 1, m, len(outs), L.hptr(rad),
+    rc = lib.toda_ball_query_stack(_ptr_rows(v), n, L.ptr(xs), L.ptr(nx), L.ptr(ns_), xs.shape[0] - 1, m, len(outs), L.hptr(rad),
                                    L.hptr(nsh), ip, ep, L.stream())
     L.check(rc, "toda_ball_query_stack")
     return outs
-
-
-def _neighbour_table(idx, empty, n):
-    """Inverse table of idx [M, ns] over n rows (toda_voxel_pool_table): off [n + 1], ent [M ns] entries per row, ascending."""
-    lib = L.load()
-    m, ns = idx.shape
-    off = torch.empty((n + 1,), dtype=torch.int32, device=idx.device)
-    ent = torch.empty((max(m * ns, 1),), dtype=torch.int32, device=idx.device)
-    nbytes = lib.toda_voxel_pool_table_bytes(m, ns, n)
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=idx.device)
-    rc = lib.toda_voxel_pool_table(L.ptr(idx), L.ptr(empty), m, ns, n, L.ptr(off), L.ptr(ent), L.ptr(ws), nbytes, L.stream())
-    L.check(rc, "toda_voxel_pool_table")
-    return off, ent
 
 
 class _SAGather(torch.autograd.Function):
@@ -2050,7 +2050,7 @@ class _SAGather(torch.autograd.Function):
         n, c = P.shape
         m, ns = idx.shape
         z = torch.empty((m * ns, c), dtype=torch.float32, device=P.device)
-        rc = lib.toda_sa_gather_fwd(L.ptr(P) if n else None, n, c, L.ptr(wd), L.ptr(idx), L.ptr(empty), m, ns, L.ptr(xyz) if n else None,
+        rc = lib.toda_sa_gather_fwd(_ptr_rows(P), n, c, L.ptr(wd), L.ptr(idx), L.ptr(empty), m, ns, _ptr_rows(xyz),
                                     L.ptr(new_xyz), L.ptr(z), L.stream())
         L.check(rc, "toda_sa_gather_fwd")
         ctx.save_for_backward(idx, empty, xyz, new_xyz)
@@ -2073,7 +2073,7 @@ class _SAGather(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             ws = torch.empty((lib.toda_sa_gather_bwd_pos_doubles(c),), dtype=torch.float64, device=gz.device)
             gwd = torch.empty((c, 3), dtype=torch.float32, device=gz.device)
-            rc = lib.toda_sa_gather_bwd_pos(L.ptr(gz), L.ptr(idx), L.ptr(empty), m, ns, c, L.ptr(xyz) if n else None, n, L.ptr(new_xyz),
+            rc = lib.toda_sa_gather_bwd_pos(L.ptr(gz), L.ptr(idx), L.ptr(empty), m, ns, c, _ptr_rows(xyz), n, L.ptr(new_xyz),
                                             L.ptr(ws), L.ptr(gwd), L.stream())
             L.check(rc, "toda_sa_gather_bwd_pos")
         return gP, gwd, None, None, None, None
