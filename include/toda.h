@@ -406,6 +406,27 @@ int toda_center_assign(const float* gt_boxes, int batch, int n_gt, int code_size
                        void* stream);
 
 /* ------------------------------------------------------------------------
+ * Anchor target assignment (pcdet/models/dense_heads/target_assigner/axis_aligned_target_assigner.py:36-210 with
+ * POS_FRACTION < 0, NORM_BY_NUM_EXAMPLES False, MATCH_HEIGHT False) for the whole batch and every anchor class: two launches,
+ * nothing read back.  anchors_host: n_classes device pointers to the class tables [locs = nz*ny*nx, per_loc = sizes*rotations,
+ * anchor_stride >= 7]; gt_boxes [B, M, gt_stride >= 8], class id (1-based, 0 = padding) in the last column; slot_of [n_ids]
+ * (device) maps a class id to its anchor class, -1 for none.  Nearest-axis BEV IoU in fp32 with the operation order of
+ * box_utils.boxes3d_nearest_bev_iou; per anchor the best gt (lowest index on a tie), per gt the maximum over the anchors;
+ * positive: best >= matched or IoU == a gt's non-zero maximum; background (0): best < unmatched; otherwise -1.
+ * targets = ResidualCoder.encode_torch of the best gt for positives (code_size = 6 + (sincos ? 2 : 1) + extra columns
+ * shared by anchors and gts), zero elsewhere; weights = 1 on positives.  multihead_order 0: rows in (z, y, x, class, size,
+ * rot) order, 1: class-major then (size, rot, z, y, x).  Integer atomics only: bit-reproducible.
+ * ws: toda_anchor_assign_workspace_bytes(batch, n_gt) bytes.
+ * ---------------------------------------------------------------------- */
+size_t toda_anchor_assign_workspace_bytes(int batch, int n_gt);
+int toda_anchor_assign(const void* const* anchors_host, const int32_t* locs_host, const int32_t* per_loc_host,
+                       const float* matched_host, const float* unmatched_host, int n_classes, int anchor_stride,
+                       const float* gt_boxes, int batch, int n_gt, int gt_stride, const int32_t* slot_of, int n_ids,
+                       int code_size, int encode_angle_by_sincos, int multihead_order,
+                       int32_t* labels /*[B, A]*/, float* targets /*[B, A, code_size]*/, float* weights /*[B, A]*/,
+                       void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Rotated BEV IoU and greedy NMS (pcdet/ops/iou3d_nms/src/iou3d_nms_kernel.cu:236-326 and the host
  * sweep of iou3d_nms.cpp:100-135, reached through model_nms_utils.class_agnostic_nms from
  * CenterHead.generate_predicted_boxes, center_head.py:291-300).  Boxes are rows of 7 floats

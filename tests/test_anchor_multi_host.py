@@ -1,0 +1,293 @@
+"""AnchorHeadMulti on the host: both new configs build with the parameter names of the reference-captured fixture, the
+screening of the fixtures' and the GPU tests' inputs holds, the torch route in both anchor orders, the head, WeightedL1Loss and
+the per-class NMS (over the oracle's rotated NMS) match the reference-captured fixtures, and ops.anchor_assign's ctypes
+prototype matches the header."""
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from tests import anchor_multi_cases as cases
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RANGE16 = [0.0, -8.0, -3.0, 16.0, 8.0, 1.0]
+
+
+def load_cfg(name):
+    from toda_amd.pcdet.config import AttrDict, cfg_from_yaml_file
+
+    cfg = AttrDict()
+    cfg_from_yaml_file(os.path.join(ROOT, "toda_amd", "tools", "cfgs", "models", f"{name}.yaml"), cfg)
+    return cfg
+
+
+def build(cfg):
+    from toda_amd.pcdet.datasets import SyntheticLidarDataset
+    from toda_amd.pcdet.models import build_network
+
+    torch.manual_seed(0)
+    return build_network(cfg.MODEL, len(cfg.CLASS_NAMES), SyntheticLidarDataset(cfg.DATA_CONFIG, cfg.CLASS_NAMES))
+
+
+def test_nuscenes_multihead_config_builds_with_reference_names():
+    from toda_amd.pcdet.models.dense_heads import AnchorHeadMulti
+
+    net = build(load_cfg("cbgs_pp_multihead_nuscenes"))
+    head = net.dense_head
+    assert isinstance(head, AnchorHeadMulti) and len(head.rpn_heads) == 6 and head.separate_multihead
+    assert [h.num_class for h in head.rpn_heads] == [1, 2, 2, 1, 2, 2]
+    assert [h.head_label_indices.tolist() for h in head.rpn_heads] == [[1], [2, 3], [4, 5], [6], [7, 8], [9, 10]]
+    assert sum(int(np.prod(a.shape[:-1])) for a in head.anchors) == 327680
+    keys = list(head.state_dict())
+    assert keys[:6] == ["shared_conv.0.weight", "shared_conv.1.weight", "shared_conv.1.bias", "shared_conv.1.running_mean",
+                        "shared_conv.1.running_var", "shared_conv.1.num_batches_tracked"]
+    per_head = [k[len("rpn_heads.1."):] for k in keys if k.startswith("rpn_heads.1.")]
+    branch = ["0.weight", "1.weight", "1.bias", "1.running_mean", "1.running_var", "1.num_batches_tracked", "3.weight", "3.bias"]
+    want = ["head_label_indices"]
+    for name in ("reg", "height", "size", "angle", "velo"):
+        want += [f"conv_box.conv_{name}.{k}" for k in branch]
+    want += [f"conv_cls.{k}" for k in branch]                 # the reference registers conv_box first
+    assert per_head == want                                   # no private neck, no direction branch
+    sd = head.state_dict()
+    assert tuple(sd["rpn_heads.1.conv_cls.3.weight"].shape) == (4 * 2, 64, 3, 3)        # 2 classes x 2 rotations anchors, 2 scores
+    assert tuple(sd["rpn_heads.1.conv_box.conv_size.3.weight"].shape) == (4 * 3, 64, 3, 3)
+    assert type(head.reg_loss_func).__name__ == "WeightedL1Loss"
+    assert len(head.rpn_heads[0].blocks) == 0 and len(head.rpn_heads[0].deblocks) == 0
+
+
+def test_kitti_multihead_config_builds_with_reference_names():
+    from toda_amd.pcdet.models.dense_heads import AnchorHeadMulti
+
+    net = build(load_cfg("second_multihead_kitti"))
+    head = net.dense_head
+    assert isinstance(head, AnchorHeadMulti) and len(head.rpn_heads) == 3
+    per_head = [k[len("rpn_heads.2."):] for k in head.state_dict() if k.startswith("rpn_heads.2.")]
+    assert per_head == ["head_label_indices", "conv_cls.weight", "conv_cls.bias", "conv_box.weight", "conv_box.bias",
+                        "conv_dir_cls.weight", "conv_dir_cls.bias"]
+    assert tuple(head.state_dict()["rpn_heads.2.conv_box.weight"].shape) == (2 * 7, 64, 1, 1)
+    assert net.model_cfg.POST_PROCESSING.NMS_CONFIG.MULTI_CLASSES_NMS
+
+
+def fixture_head_keys():
+    return [str(k) for k in cases.load("anchor_multi_head")["keys"]]
+
+
+def test_config_heads_carry_the_fixture_key_names():
+    """The fixture's head has a shared convolution, separate regression branches and a direction classifier.  The nuScenes
+    config's heads must spell every one of those keys the same way (it has no direction branch and one more regression
+    branch, conv_velo, spelled like its siblings); the KITTI config's plain heads are a different layout, pinned above."""
+    keys = fixture_head_keys()
+    head = build(load_cfg("cbgs_pp_multihead_nuscenes")).dense_head
+    mine = list(head.state_dict())
+    assert [k for k in mine if k.startswith("shared_conv.")] == [k for k in keys if k.startswith("shared_conv.")]
+    fixture_head = [k[len("rpn_heads.1."):] for k in keys if k.startswith("rpn_heads.1.") and "conv_dir_cls" not in k]
+    for i in range(6):
+        prefix = f"rpn_heads.{i}."
+        per_head = [k[len(prefix):] for k in mine if k.startswith(prefix)]
+        assert [k for k in per_head if "conv_velo" not in k] == fixture_head, i
+        assert [k.replace("conv_velo", "conv_angle") for k in per_head if "conv_velo" in k] == [k for k in per_head if "conv_angle" in k]
+    assert tuple(head.state_dict()["rpn_heads.1.conv_box.conv_velo.3.weight"].shape) == (4 * 2, 64, 3, 3)
+    assert head.box_coder.code_size == 10 and len(head.model_cfg.LOSS_CONFIG.LOSS_WEIGHTS.code_weights) == 10
+
+
+def test_fixture_screening_conditions_hold():
+    """Recomputed from the committed inputs: no best IoU within 1e-4 of a threshold, and the same maximal anchors per gt in
+    float64 and float32, for every gt set the fixtures hold."""
+    g = cases.load("anchor_multi_assign")
+    for tag, _, _ in cases.ASSIGN_CASES:
+        gt = g[f"{tag}_gt"]
+        assert cases.screening_failures(cases.fixture_anchors(g, tag), gt, cases.SMALL4) == []
+        # the cases the fixture must hold: an empty sample, one gt, a class without gt, a gt off the map, trailing padding
+        counts = [int((np.abs(gt[b]).sum(1) > 0).sum()) for b in range(3)]
+        assert counts[0] == 0 and counts[1] == 1 and counts[2] < gt.shape[1]
+        assert not (gt[:, :, -1] == 3).any() and (gt[2, :, 0] > 16.0).any()
+    h = cases.load("anchor_multi_head")
+    _, anchors = cases.make_assigner(cases.HEAD_SPECS, (16, 16), RANGE16, True)
+    assert cases.screening_failures(anchors, h["gt"], cases.HEAD_SPECS) == []
+
+
+def test_torch_route_matches_the_reference_fixture_in_both_orders():
+    cases.check_assign_fixture("torch", "cpu")
+
+
+def test_head_matches_the_reference_fixture_on_the_cpu():
+    cases.check_head_fixture("cpu")
+
+
+def oracle_nms(boxes, scores, thresh, pre_maxsize=None, **kwargs):
+    from oracle import oracle as O
+
+    order = scores.sort(0, descending=True)[1]
+    keep = O.nms_rotated(boxes[order].numpy(), thresh)
+    return order[torch.from_numpy(keep)], None
+
+
+def test_multi_classes_nms_and_post_processing_match_the_reference_fixture(monkeypatch):
+    from toda_amd.pcdet.models.model_utils import model_nms_utils
+
+    monkeypatch.setattr(model_nms_utils, "nms_gpu", oracle_nms)
+    cases.check_nms_fixture("cpu")
+
+
+def test_weighted_l1_loss_matches_the_reference_fixture():
+    from toda_amd.pcdet.utils import loss_utils
+
+    g = cases.load("anchor_multi_nms")
+    out = loss_utils.WeightedL1Loss(code_weights=g["l1_code_weights"].tolist())(
+        torch.from_numpy(g["l1_a"]), torch.from_numpy(g["l1_t"]), torch.from_numpy(g["l1_w"]))
+    np.testing.assert_allclose(out.numpy(), g["l1"], rtol=1e-5, atol=1e-7)        # check_anchor_losses' tolerance
+    assert float(out[0, 3, 2]) == 0.0
+
+
+def test_score_lists_without_multi_classes_nms_are_refused():
+    from toda_amd.pcdet.config import AttrDict
+    from toda_amd.pcdet.models.detectors.detector3d_template import Detector3DTemplate
+
+    class Stub(Detector3DTemplate):
+        def __init__(self):
+            torch.nn.Module.__init__(self)
+            self.num_class = 2
+            self.model_cfg = AttrDict(dict(POST_PROCESSING=dict(cases.NMS_CFG, NMS_CONFIG=dict(cases.NMS_CFG["NMS_CONFIG"], MULTI_CLASSES_NMS=False))))
+
+    batch = {"batch_size": 1, "batch_box_preds": torch.zeros(1, 2, 7), "batch_cls_preds": [torch.zeros(1, 1, 1), torch.zeros(1, 1, 1)],
+             "cls_preds_normalized": True}
+    with pytest.raises(NotImplementedError):
+        Stub().post_processing(batch)
+
+
+def test_head_forward_shapes_label_mapping_and_losses_on_the_cpu():
+    net = build(load_cfg("second_multihead_kitti"))
+    head = net.dense_head.train()
+    head.predict_boxes_when_training = True
+    gt = torch.from_numpy(cases.draw_gt(3, cases.KITTI3, [0.0, -40.0, -3.0, 70.4, 40.0, 1.0], 2, 6))
+    d = head({"spatial_features_2d": torch.randn(2, 512, 200, 176) * 0.1, "batch_size": 2, "gt_boxes": gt})
+    assert [tuple(t.shape) for t in d["batch_cls_preds"]] == [(2, 70400, 1)] * 3
+    assert tuple(d["batch_box_preds"].shape) == (2, 211200, 7)
+    assert [m.tolist() for m in d["multihead_label_mapping"]] == [[1], [2], [3]]
+    loss, tb = head.get_loss()
+    assert torch.isfinite(loss) and set(tb) == {"rpn_loss_cls", "rpn_loss_loc", "rpn_loss_dir", "rpn_loss"}
+    assert all(isinstance(v, torch.Tensor) for v in tb.values())          # log values stay tensors
+    loss.backward()
+    assert all(p.grad is not None for p in head.parameters())
+
+
+@pytest.mark.parametrize("code_size,sincos,n_extra", [(7, False, 0), (9, True, 2)])
+def test_multihead_order_of_the_torch_route_is_the_single_head_result_reordered(code_size, sincos, n_extra):
+    multi, anchors = cases.make_assigner(cases.SMALL4, (16, 16), RANGE16, True, code_size, sincos)
+    single, _ = cases.make_assigner(cases.SMALL4, (16, 16), RANGE16, False, code_size, sincos)
+    gt = torch.from_numpy(cases.draw_gt(5, cases.SMALL4, RANGE16, 2, 8, n_extra=n_extra))
+    assert multi.route(gt) == "torch"                          # host tensors never reach the kernel
+    m, s = multi.assign_targets(anchors, gt.clone()), single.assign_targets(anchors, gt.clone())
+    assert int((s["box_cls_labels"] > 0).sum()) > 0
+    code = multi.box_coder.code_size
+    for key, tail in (("box_cls_labels", ()), ("reg_weights", ()), ("box_reg_targets", (code,))):
+        per_class = s[key].view(2, 1, 16, 16, 4, 1, 2, *tail)              # (b, z, y, x, class, size, rot)
+        want = torch.cat([per_class[:, :, :, :, c].permute(0, 4, 5, 1, 2, 3, *range(6, 6 + len(tail))).reshape(2, -1, *tail)
+                          for c in range(4)], dim=1)
+        assert torch.equal(m[key], want), key
+
+
+def test_screening_of_the_gpu_test_inputs_holds_and_rejects():
+    _, anchors = cases.make_assigner(cases.SMALL4, (16, 16), RANGE16, True)
+    gt = cases.screened_gt(11, anchors, cases.SMALL4, RANGE16, 3, 12, counts=[0, 1, 9], class_pool=[0, 1, 3])
+    assert cases.screening_failures(anchors, gt, cases.SMALL4) == []
+    # a gt that reproduces an anchor exactly has IoU 1 with it; a copy scaled to IoU = matched sits on the threshold
+    a = anchors[0][0, 4, 4, 0, 0].numpy()
+    on = np.zeros((1, 1, 8), np.float32)
+    on[0, 0, :7] = a[:7]
+    on[0, 0, 3] *= np.float32(0.6)
+    on[0, 0, -1] = 1
+    assert ("threshold" in [r for _, _, r in cases.screening_failures(anchors, on, cases.SMALL4)])
+
+
+def test_weighted_l1_loss():
+    from toda_amd.pcdet.utils import loss_utils
+
+    g = torch.Generator().manual_seed(0)
+    a, b, w = torch.randn(2, 5, 3, generator=g), torch.randn(2, 5, 3, generator=g), torch.rand(2, 5, generator=g)
+    b[0, 1, 2] = float("nan")                                   # nan targets are ignored
+    out = loss_utils.WeightedL1Loss(code_weights=[1.0, 2.0, 0.5])(a, b, w)
+    want = (a - torch.where(torch.isnan(b), a, b)).abs() * torch.tensor([1.0, 2.0, 0.5]) * w[..., None]
+    torch.testing.assert_close(out, want, rtol=0, atol=0)
+    assert float(out[0, 1, 2]) == 0.0
+    torch.testing.assert_close(loss_utils.WeightedL1Loss()(a, b), (a - torch.where(torch.isnan(b), a, b)).abs(), rtol=0, atol=0)
+
+
+def test_multi_classes_nms_with_a_cpu_stand_in(monkeypatch):
+    from toda_amd.pcdet.config import AttrDict
+    from toda_amd.pcdet.models.model_utils import model_nms_utils
+
+    def greedy(boxes, scores, thresh, **kw):                    # axis-aligned greedy NMS, input order = score order
+        order = scores.sort(0, descending=True)[1]
+        rect = torch.cat([boxes[:, :2] - boxes[:, 3:5] / 2, boxes[:, :2] + boxes[:, 3:5] / 2], 1)[order]
+        keep = []
+        for i in range(len(order)):
+            ok = True
+            for j in keep:
+                wh = (torch.min(rect[i, 2:], rect[j, 2:]) - torch.max(rect[i, :2], rect[j, :2])).clamp(min=0)
+                inter = wh[0] * wh[1]
+                area = lambda r: (r[2] - r[0]) * (r[3] - r[1])  # noqa: E731
+                ok = ok and float(inter / (area(rect[i]) + area(rect[j]) - inter)) <= thresh
+            if ok:
+                keep.append(i)
+        return order[torch.tensor(keep, dtype=torch.long)], None
+
+    monkeypatch.setattr(model_nms_utils, "nms_gpu", greedy)
+    cfg = AttrDict(dict(NMS_TYPE="nms_gpu", NMS_THRESH=0.1, NMS_PRE_MAXSIZE=4, NMS_POST_MAXSIZE=2))
+    boxes = torch.tensor([[0.0, 0, 0, 2, 2, 1, 0], [0.1, 0, 0, 2, 2, 1, 0], [10.0, 0, 0, 2, 2, 1, 0], [20.0, 0, 0, 2, 2, 1, 0],
+                          [30.0, 0, 0, 2, 2, 1, 0]])
+    scores = torch.tensor([[0.9, 0.05], [0.8, 0.6], [0.7, 0.05], [0.6, 0.5], [0.5, 0.05]])
+    s, l, b = model_nms_utils.multi_classes_nms(scores, boxes, cfg, score_thresh=0.1)
+    # class 0: top-4 of 5, the near-duplicate goes, the best two of the rest stay; class 1: only the two above the threshold
+    assert l.tolist() == [0, 0, 1, 1] and l.dtype == torch.long
+    torch.testing.assert_close(s, torch.tensor([0.9, 0.7, 0.6, 0.5]))
+    assert b[:, 0].tolist() == [0.0, 10.0, pytest.approx(0.1), 20.0]
+    s, l, b = model_nms_utils.multi_classes_nms(scores, boxes, cfg, score_thresh=0.95)
+    assert s.numel() == 0 and l.numel() == 0 and tuple(b.shape) == (0, 7)
+
+
+def test_named_refusals_are_gone_and_the_others_stay():
+    from toda_amd.pcdet.models.dense_heads import __all__ as heads
+
+    assert "AnchorHeadMulti" in heads
+    assigner, _ = cases.make_assigner(cases.KITTI3, (8, 8), RANGE16, True)
+    assert assigner.use_multihead
+    from toda_amd.pcdet.models.dense_heads.target_assigner.axis_aligned_target_assigner import AxisAlignedTargetAssigner
+    with pytest.raises(NotImplementedError):
+        AxisAlignedTargetAssigner(cases.head_cfg(cases.KITTI3, True), ["Car", "Pedestrian", "Cyclist"], assigner.box_coder, match_height=True)
+
+
+def header_arg_count(name):
+    text = open(os.path.join(ROOT, "include", "toda.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    m = re.search(r"\b(\w[\w\s\*]*?)\b" + name + r"\s*\(([^;]*?)\)\s*;", text, flags=re.S)
+    assert m, name
+    return m.group(1).strip(), [a.strip() for a in m.group(2).split(",")]
+
+
+def test_anchor_assign_prototype_matches_the_header_and_validates():
+    import ctypes as C
+
+    from toda_amd import lib as L
+
+    for name in ("toda_anchor_assign", "toda_anchor_assign_workspace_bytes"):
+        ret, args = header_arg_count(name)
+        res, argtypes = L.SIGNATURES[name]
+        assert len(argtypes) == len(args), name
+        assert res is (C.c_size_t if ret == "size_t" else C.c_int)
+        for decl, ct in zip(args, argtypes):
+            want = C.c_void_p if "*" in decl else C.c_size_t if decl.startswith("size_t") else C.c_int
+            assert ct is want, (name, decl)
+    lib = L.load()
+    assert lib.toda_anchor_assign_workspace_bytes(4, 40) >= 4 * 40 * 4
+    one = L.host_f32([0.5])
+    i1 = L.host_i32([4])
+    ptrs = (C.c_void_p * 1)(1)
+    call = lambda **kw: lib.toda_anchor_assign(  # noqa: E731
+        L.hptr(ptrs), L.hptr(i1), L.hptr(i1), L.hptr(one), L.hptr(one), kw.get("n_classes", 1), 7, L.hptr(one), 1, 1, 8, L.hptr(i1), 1,
+        kw.get("code", 7), 0, 1, L.hptr(one), L.hptr(one), L.hptr(one), L.hptr(one), kw.get("ws", 256), None)
+    assert call(code=9) == -1 and b"code size" in lib.toda_last_error()
+    assert call(n_classes=0) == -1 and b"anchor classes" in lib.toda_last_error()
+    assert call(ws=0) == -1 and b"workspace" in lib.toda_last_error()

@@ -149,6 +149,8 @@ SIGNATURES = {
     "toda_timing_begin": (_i, [_i]),
     "toda_timing_end": (_i, [_vp, _i, _vp]),
     "toda_center_assign": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _dbl, _i, _vp, _vp, _vp, _vp, _vp]),
+    "toda_anchor_assign_workspace_bytes": (_sz, [_i, _i]),
+    "toda_anchor_assign": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

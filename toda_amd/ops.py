@@ -1728,6 +1728,43 @@ def center_assign(gt_boxes, num_classes, fm_w, fm_h, pc_range, voxel_size, fm_st
     return hm, rb, inds, mask
 
 
+# --------------------------------------------------------------- anchor-head target assign
+def anchor_assign(anchors, gt_boxes, slot_of, matched, unmatched, code_size, encode_angle_by_sincos=False, multihead=False):
+    """AxisAlignedTargetAssigner.assign_targets for the whole batch and every anchor class in two launches, nothing read back.
+    anchors: the per-class tables [nz, ny, nx, sizes, rots, >= 7] as the head holds them; gt_boxes [B, M, 7 + C + 1];
+    slot_of int32 [n_ids]: class id -> index into `anchors` (-1: none); matched / unmatched: per-class thresholds.
+    Returns box_cls_labels int32 [B, A], box_reg_targets fp32 [B, A, code_size], reg_weights fp32 [B, A]; the rows run
+    (z, y, x, class, size, rot), or class-major then (size, rot, z, y, x) when `multihead`."""
+    lib = L.load()
+    gt = gt_boxes if (gt_boxes.dtype == torch.float32 and gt_boxes.is_contiguous()) else gt_boxes.to(torch.float32).contiguous()
+    batch, n_gt, gt_stride = gt.shape
+    dev = gt.device
+    stride = int(anchors[0].shape[-1])
+    tables = []
+    for a in anchors:
+        if a.dim() != 6 or a.shape[-1] != stride or a.dtype != torch.float32 or not a.is_contiguous() or a.device != dev:
+            raise RuntimeError("anchor_assign: the anchor tables must be contiguous fp32 [nz, ny, nx, sizes, rots, C] with one C, "
+                               "on the gt boxes' device")
+        tables.append(a)
+    if slot_of.dtype != torch.int32 or slot_of.dim() != 1 or not slot_of.is_contiguous() or slot_of.device != dev:
+        raise RuntimeError("anchor_assign: slot_of must be a contiguous int32 vector on the gt boxes' device")
+    locs = [int(a.shape[0] * a.shape[1] * a.shape[2]) for a in tables]
+    per_loc = [int(a.shape[3] * a.shape[4]) for a in tables]
+    total = sum(n * k for n, k in zip(locs, per_loc))
+    labels = torch.empty((batch, total), dtype=torch.int32, device=dev)
+    targets = torch.empty((batch, total, int(code_size)), dtype=torch.float32, device=dev)
+    weights = torch.empty((batch, total), dtype=torch.float32, device=dev)
+    ws_bytes = lib.toda_anchor_assign_workspace_bytes(batch, n_gt)
+    ws = torch.empty((max(int(ws_bytes), 1),), dtype=torch.uint8, device=dev)
+    rc = lib.toda_anchor_assign(L.hptr(L.host_ptrs(tables)), L.hptr(L.host_i32(locs)), L.hptr(L.host_i32(per_loc)),
+                                L.hptr(L.host_f32(matched)), L.hptr(L.host_f32(unmatched)), len(tables), stride, L.ptr(gt),
+                                batch, n_gt, gt_stride, L.ptr(slot_of), int(slot_of.numel()), int(code_size),
+                                int(bool(encode_angle_by_sincos)), int(bool(multihead)), L.ptr(labels), L.ptr(targets),
+                                L.ptr(weights), L.ptr(ws), ws_bytes, L.stream())
+    L.check(rc, "toda_anchor_assign")
+    return labels, targets, weights
+
+
 class _CenterLoss(torch.autograd.Function):
     """CenterHead.get_loss of one head group in three launches forward / one backward (toda_center_loss_*).
     apply(n, hm_logits, reg_0..reg_{n-1}, heatmap, inds, mask, target_boxes, code_weights, cls_weight, loc_weight)

@@ -64,7 +64,8 @@ def synth_cloud(kind, seed, n_points=None, n_boxes=30, class_count=3):
 
 class SyntheticLidarDataset(DatasetTemplate):
     """dataset_cfg keys: POINT_CLOUD_RANGE, POINT_FEATURE_ENCODING, DATA_PROCESSOR (as the
-    reference's dataset YAMLs) + SYNTHETIC: {KIND | KINDS, NUM_SAMPLES, SEED, NUM_POINTS}."""
+    reference's dataset YAMLs) + SYNTHETIC: {KIND | KINDS, NUM_SAMPLES, SEED, NUM_POINTS, BOX_VELOCITY}.  BOX_VELOCITY: True
+    gives the training boxes two more columns (vx, vy along the heading, the nuScenes box layout); infos and evaluation keep 7."""
 
     def __init__(self, dataset_cfg, class_names, training=True, root_path=None, logger=None):
         super().__init__(dataset_cfg=dataset_cfg, class_names=class_names, training=training, root_path=root_path,
@@ -74,6 +75,7 @@ class SyntheticLidarDataset(DatasetTemplate):
         self.num_samples = int(syn.get("NUM_SAMPLES", 64))
         self.seed = int(syn.get("SEED", 0))
         self.num_points = syn.get("NUM_POINTS", None)
+        self.box_velocity = bool(syn.get("BOX_VELOCITY", False))
         # pseudo-label round trip (reference nuscenes_dataset.py include_nuscenes_data + INFO_PATH['pseudo']): an infos
         # pickle written by tools/generate_pseudo_labels.py replaces the frames' ground truth
         self.pseudo_infos = None
@@ -155,6 +157,10 @@ class SyntheticLidarDataset(DatasetTemplate):
 
     def __getitem__(self, index):
         points, boxes, names = self.raw_sample(index)
+        if self.box_velocity:
+            speed = np.random.default_rng(77_000_003 + self.seed + index).uniform(-3.0, 3.0, len(boxes))
+            velo = np.stack([speed * np.cos(boxes[:, 6]), speed * np.sin(boxes[:, 6])], 1).astype(np.float32)
+            boxes = np.concatenate([boxes[:, :7], velo], 1)
         data = {"points": points, "gt_boxes": boxes, "gt_names": names, "frame_id": self.frame_id(index),
                 "_rng": np.random.default_rng(10_000_019 * (self.seed + 1) + index)}
         return self.prepare_data(data)

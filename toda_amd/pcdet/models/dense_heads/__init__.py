@@ -1,3 +1,4 @@
+from .anchor_head_multi import AnchorHeadMulti
 from .anchor_head_single import AnchorHeadSingle
 from .anchor_head_template import AnchorHeadTemplate
 from .center_head import CenterHead
@@ -5,5 +6,6 @@ from .center_head import CenterHead
 __all__ = {
     "AnchorHeadTemplate": AnchorHeadTemplate,
     "AnchorHeadSingle": AnchorHeadSingle,
+    "AnchorHeadMulti": AnchorHeadMulti,
     "CenterHead": CenterHead,
 }

@@ -59,7 +59,12 @@ class AnchorHeadTemplate(nn.Module):
         return self.target_assigner.assign_targets(self.anchors, gt_boxes)
 
     def _flat_anchors(self):
-        a = torch.cat(self.anchors, dim=-3) if isinstance(self.anchors, list) else self.anchors
+        """[1, A, code] in the order of the predictions: (z, y, x, class, size, rot), or with USE_MULTIHEAD class-major then
+        (size, rot, z, y, x) (reference anchor_head_template.py:238-245)."""
+        if isinstance(self.anchors, list) and self.use_multihead:
+            a = torch.cat([t.permute(3, 4, 0, 1, 2, 5).contiguous().view(-1, t.shape[-1]) for t in self.anchors], dim=0)
+        else:
+            a = torch.cat(self.anchors, dim=-3) if isinstance(self.anchors, list) else self.anchors
         return a.view(1, -1, a.shape[-1])
 
     def get_cls_layer_loss(self):
@@ -138,10 +143,16 @@ class AnchorHeadTemplate(nn.Module):
         anchors = self._flat_anchors()
         n = anchors.shape[1]
         batch_anchors = anchors.repeat(batch_size, 1, 1)
-        batch_cls = cls_preds.view(batch_size, n, -1).float()
+        # separate multi-head predictions arrive as one tensor per head: the class scores stay a list (each head has its own
+        # classes), boxes and direction bins are joined along the anchors (reference :248-258)
+        batch_cls = cls_preds if isinstance(cls_preds, list) else cls_preds.view(batch_size, n, -1).float()
+        if isinstance(box_preds, list):
+            box_preds = torch.cat(box_preds, dim=1)
         batch_box = self.box_coder.decode_torch(box_preds.view(batch_size, n, -1), batch_anchors)
         if dir_cls_preds is not None:
             offset, limit = self.model_cfg.DIR_OFFSET, self.model_cfg.DIR_LIMIT_OFFSET
+            if isinstance(dir_cls_preds, list):
+                dir_cls_preds = torch.cat(dir_cls_preds, dim=1)
             dir_labels = torch.max(dir_cls_preds.view(batch_size, n, -1), dim=-1)[1]
             period = 2 * np.pi / self.model_cfg.NUM_DIR_BINS
             rot = common_utils.limit_period(batch_box[..., 6] - offset, limit, period)

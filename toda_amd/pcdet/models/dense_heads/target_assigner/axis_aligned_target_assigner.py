@@ -1,9 +1,18 @@
 """AxisAlignedTargetAssigner (reference target_assigner/axis_aligned_target_assigner.py:8-210):
 per class, anchors are matched to that class's gt boxes by nearest-axis BEV IoU; anchors above
 matched_threshold (and each gt's best anchor) become positives, below unmatched_threshold
-negatives, the rest are ignored (-1).  Regression targets come from the box coder."""
+negatives, the rest are ignored (-1).  Regression targets come from the box coder.
+
+Two routes.  The HIP route (ops.anchor_assign, toda_anchor_assign) assigns the whole batch for all classes in two launches
+without reading anything back; it serves the configs without random sampling (POS_FRACTION < 0, NORM_BY_NUM_EXAMPLES
+False).  The torch route below is the reference's loop and serves everything else.  TODA_ANCHOR_ASSIGN picks:
+`auto` (default) HIP for multi-head order only, `hip` both orders, `torch` neither."""
+import os
+
 import numpy as np
 import torch
+
+from toda_amd import ops
 
 from ....utils import box_utils
 
@@ -23,11 +32,40 @@ class AxisAlignedTargetAssigner:
         self.matched_thresholds = {c["class_name"]: c["matched_threshold"] for c in gen_cfg}
         self.unmatched_thresholds = {c["class_name"]: c["unmatched_threshold"] for c in gen_cfg}
         self.use_multihead = model_cfg.get("USE_MULTIHEAD", False)
-        if self.use_multihead:
-            raise NotImplementedError("AnchorHeadMulti is not on the named path (DESIGN.md)")
+        # class id (1-based, 0 = padding) -> index of its anchor class, -1: none; on the device after the first HIP call
+        name_to_slot = {n: i for i, n in enumerate(self.anchor_class_names)}
+        self._slot_host = torch.tensor([-1] + [name_to_slot.get(n, -1) for n in class_names], dtype=torch.int32)
+        self._slot_dev = None
+
+    def route(self, gt_boxes):
+        """'hip' or 'torch' for this call (TODA_ANCHOR_ASSIGN, module docstring)."""
+        mode = os.environ.get("TODA_ANCHOR_ASSIGN", "auto")
+        if mode not in ("auto", "hip", "torch"):
+            raise ValueError(f"TODA_ANCHOR_ASSIGN={mode}: expected auto, hip or torch")
+        eligible = self.pos_fraction is None and not self.norm_by_num_examples and gt_boxes.is_cuda
+        if mode == "torch" or not eligible:
+            return "torch"
+        return "hip" if (mode == "hip" or self.use_multihead) else "torch"
 
     def assign_targets(self, all_anchors, gt_boxes_with_classes):
-        """all_anchors: list over classes of [nz,ny,nx,ns,nr,7]; gt [B, M, 8] -> dict of [B, A(, code)]."""
+        """all_anchors: list over classes of [nz,ny,nx,ns,nr,7+C]; gt [B, M, 7+C+1] -> dict of [B, A(, code)].  Rows run
+        (z, y, x, class, size, rot); with USE_MULTIHEAD class-major, then (size, rot, z, y, x)."""
+        if self.route(gt_boxes_with_classes) == "hip":
+            return self.assign_targets_hip(all_anchors, gt_boxes_with_classes)
+        return self.assign_targets_torch(all_anchors, gt_boxes_with_classes)
+
+    def assign_targets_hip(self, all_anchors, gt_boxes_with_classes):
+        dev = gt_boxes_with_classes.device
+        if self._slot_dev is None or self._slot_dev.device != dev:
+            self._slot_dev = self._slot_host.to(dev)
+        labels, targets, weights = ops.anchor_assign(
+            all_anchors, gt_boxes_with_classes, self._slot_dev,
+            [self.matched_thresholds[n] for n in self.anchor_class_names],
+            [self.unmatched_thresholds[n] for n in self.anchor_class_names],
+            self.box_coder.code_size, getattr(self.box_coder, "encode_angle_by_sincos", False), self.use_multihead)
+        return {"box_cls_labels": labels, "box_reg_targets": targets, "reg_weights": weights}
+
+    def assign_targets_torch(self, all_anchors, gt_boxes_with_classes):
         code = self.box_coder.code_size
         reg_all, cls_all, w_all = [], [], []
         for gt in gt_boxes_with_classes:
@@ -40,9 +78,15 @@ class AxisAlignedTargetAssigner:
             for cls_name, anchors in zip(self.anchor_class_names, all_anchors):
                 sel = torch.from_numpy(np.asarray(names == cls_name, dtype=bool).reshape(-1)).to(gt.device)
                 fmap = anchors.shape[:3]
-                t = self.assign_targets_single(anchors.view(-1, anchors.shape[-1]), boxes[sel], classes[sel],
+                flat = (anchors.permute(3, 4, 0, 1, 2, 5).contiguous() if self.use_multihead else anchors).view(-1, anchors.shape[-1])
+                t = self.assign_targets_single(flat, boxes[sel], classes[sel],
                                                self.matched_thresholds[cls_name], self.unmatched_thresholds[cls_name])
                 per_class.append((t, fmap))
+            if self.use_multihead:
+                cls_all.append(torch.cat([t["box_cls_labels"].view(-1) for t, _ in per_class]))
+                reg_all.append(torch.cat([t["box_reg_targets"].view(-1, code) for t, _ in per_class]))
+                w_all.append(torch.cat([t["reg_weights"].view(-1) for t, _ in per_class]))
+                continue
             cls_all.append(torch.cat([t["box_cls_labels"].view(*f, -1) for t, f in per_class], dim=-1).view(-1))
             reg_all.append(torch.cat([t["box_reg_targets"].view(*f, -1, code) for t, f in per_class], dim=-2).view(-1, code))
             w_all.append(torch.cat([t["reg_weights"].view(*f, -1) for t, f in per_class], dim=-1).view(-1))

@@ -157,13 +157,15 @@ class Detector3DTemplate(nn.Module):
 
     # ------------------------------------------------------------- evaluation
     def post_processing(self, batch_dict):
-        """Single-head, class-agnostic-NMS branch of the reference (detector3d_template.py:178-284): per sample sigmoid
-        scores -> best class -> rotated NMS on the device -> pred dicts, plus the recall record."""
+        """Reference detector3d_template.py:178-284: per sample sigmoid scores, then either the best class and one
+        class-agnostic rotated NMS, or (MULTI_CLASSES_NMS / the per-head score lists of a separate multi-head) one NMS per
+        class with the heads' label mapping -> pred dicts, plus the recall record."""
         from ..model_utils import model_nms_utils
 
         cfg = self.model_cfg.POST_PROCESSING
-        if cfg.NMS_CONFIG.get("MULTI_CLASSES_NMS", False) or isinstance(batch_dict["batch_cls_preds"], list):
-            raise NotImplementedError("multi-class / multi-head NMS is not on this path")
+        multi = cfg.NMS_CONFIG.get("MULTI_CLASSES_NMS", False)
+        if isinstance(batch_dict["batch_cls_preds"], list) and not multi:
+            raise NotImplementedError("per-head class scores (SEPARATE_MULTIHEAD) need NMS_CONFIG.MULTI_CLASSES_NMS: True")
         recall_dict, pred_dicts = {}, []
         for index in range(batch_dict["batch_size"]):
             if batch_dict.get("batch_index", None) is not None:
@@ -171,6 +173,26 @@ class Detector3DTemplate(nn.Module):
             else:
                 pick = index
             box_preds = batch_dict["batch_box_preds"][pick]
+            if multi:
+                heads = batch_dict["batch_cls_preds"]
+                if isinstance(heads, list):
+                    heads, mapping = [h[pick] for h in heads], batch_dict["multihead_label_mapping"]
+                else:
+                    heads, mapping = [heads[pick]], [torch.arange(1, self.num_class + 1, device=box_preds.device)]
+                if not batch_dict["cls_preds_normalized"]:
+                    heads = [torch.sigmoid(h) for h in heads]
+                start, parts = 0, []
+                for scores, labels_of in zip(heads, mapping):
+                    assert scores.shape[1] == len(labels_of)
+                    s, l, b = model_nms_utils.multi_classes_nms(cls_scores=scores, box_preds=box_preds[start:start + scores.shape[0]],
+                                                                nms_config=cfg.NMS_CONFIG, score_thresh=cfg.SCORE_THRESH)
+                    parts.append((s, labels_of.to(l.device)[l], b))
+                    start += scores.shape[0]
+                final_scores, final_labels, final_boxes = (torch.cat([p[i] for p in parts], dim=0) for i in range(3))
+                recall_dict = self.generate_recall_record(final_boxes if "rois" not in batch_dict else box_preds, recall_dict, index,
+                                                          batch_dict, cfg.RECALL_THRESH_LIST)
+                pred_dicts.append({"pred_boxes": final_boxes, "pred_scores": final_scores, "pred_labels": final_labels})
+                continue
             raw_cls = batch_dict["batch_cls_preds"][pick]
             cls_preds = raw_cls if batch_dict["cls_preds_normalized"] else torch.sigmoid(raw_cls)
             scores, labels = torch.max(cls_preds, dim=-1)

@@ -30,3 +30,25 @@ def class_agnostic_nms(box_scores, box_preds, nms_config, score_thresh=None):
     if score_thresh is not None:
         selected = scores_mask.nonzero().view(-1)[selected]
     return selected, src_scores[selected]
+
+
+def multi_classes_nms(cls_scores, box_preds, nms_config, score_thresh=None):
+    """Per class column of cls_scores [N, C]: score mask, top-k, rotated NMS, NMS_POST_MAXSIZE (reference :28-66).
+    Returns scores, labels (0-based column, int64) and boxes of the kept predictions, class after class."""
+    if nms_config.NMS_TYPE != "nms_gpu":
+        raise NotImplementedError(f"NMS_TYPE {nms_config.NMS_TYPE}: only nms_gpu (rotated BEV) is on this path")
+    scores_out, labels_out, boxes_out = [], [], []
+    for k in range(cls_scores.shape[1]):
+        scores, boxes = cls_scores[:, k], box_preds
+        if score_thresh is not None:
+            mask = scores >= score_thresh
+            scores, boxes = scores[mask], boxes[mask]
+        selected = scores.new_zeros((0,), dtype=torch.long)
+        if scores.shape[0] > 0:
+            top_scores, indices = torch.topk(scores, k=min(nms_config.NMS_PRE_MAXSIZE, scores.shape[0]))
+            keep_idx, _ = nms_gpu(boxes[indices][:, 0:7], top_scores, nms_config.NMS_THRESH)
+            selected = indices[keep_idx[:nms_config.NMS_POST_MAXSIZE]]
+        scores_out.append(scores[selected])
+        labels_out.append(torch.full((selected.shape[0],), k, dtype=torch.long, device=scores.device))
+        boxes_out.append(boxes[selected])
+    return torch.cat(scores_out, dim=0), torch.cat(labels_out, dim=0), torch.cat(boxes_out, dim=0)

@@ -115,6 +115,30 @@ class WeightedSmoothL1Loss(nn.Module):
         return loss
 
 
+class WeightedL1Loss(nn.Module):
+    """|input - target| per code dimension with code and anchor weights (reference loss_utils.py:124-164)."""
+
+    def __init__(self, code_weights=None):
+        super().__init__()
+        self.code_weights = None
+        if code_weights is not None:
+            self.register_buffer("_cw", torch.tensor(code_weights, dtype=torch.float32), persistent=False)
+            self.code_weights = code_weights
+
+    def forward(self, input, target, weights=None):
+        target = torch.where(torch.isnan(target), input, target)  # ignore nan targets
+        diff = input - target
+        if self.code_weights is not None:
+            if self._cw.device != diff.device:
+                self._cw = self._cw.to(diff.device)
+            diff = diff * self._cw.view(1, 1, -1)
+        loss = torch.abs(diff)
+        if weights is not None:
+            assert weights.shape[0] == loss.shape[0] and weights.shape[1] == loss.shape[1]
+            loss = loss * weights.unsqueeze(-1)
+        return loss
+
+
 class WeightedCrossEntropyLoss(nn.Module):
     def forward(self, input, target, weights):
         """input [B, A, C] logits, target [B, A, C] one-hot, weights [B, A] -> [B, A]"""
