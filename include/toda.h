@@ -748,6 +748,44 @@ int toda_clip_adam_step(const unsigned long long* param, const unsigned long lon
                         const long long* chunk_off, int n_chunks, double* partial, float* norm_out, float max_norm,
                         float lr, float beta1, float beta2, float eps, float weight_decay, int step, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The device parts of the KITTI AP evaluator (reference pcdet/datasets/kitti/kitti_object_eval_python: rotate_iou.py, a
+ * numba-CUDA kernel, and eval.py:87-154 image_box_overlap / d3_box_overlap, eval.py:157-337 compute_statistics_jit /
+ * fused_compute_statistics, numba-JIT host loops).  Boxes and queries of F frames are given flat with CSR offsets
+ * (int32 [F + 1]); only same-frame pairs are computed.
+ *
+ * toda_eval_overlaps: out + out_off[f] holds frame f's [n_box_f, n_query_f] block, row major, fp32 (out_off: int64 [F + 1],
+ * n_pairs = out_off[F]).  box3d / query3d rows: x, y, z, l, h, w, rotation_y in the KITTI camera frame (y the bottom face);
+ * bbox / query_bbox rows: x1, y1, x2, y2; the set a metric does not read may be NULL.
+ *   metric 0  image boxes            criterion -1: inter / union, 0: / box area, 1: / query area, 2: / 1
+ *   metric 1  BEV rectangles (x, z, l, w, ry): exact clipping with no corner margin, angles clockwise-positive, fp32;
+ *             the reference hands its device function the QUERY first, so criterion 0: / query area, 1: / box area,
+ *             2: the intersection area
+ *   metric 2  BEV intersection x overlap of [y - h, y]; criterion 0: / box volume, 1: / query volume, 2: / itself
+ *
+ * toda_eval_match: for one (class, difficulty, min_overlap, metric) the greedy assignment of every frame at every one of the
+ * n_thresh score thresholds, pr[n_thresh, 4] = (tp, fp, fn, AOS similarity) summed over the frames in a fixed order (two
+ * runs: same bits).  overlaps / ov_off as written by toda_eval_overlaps with the detections as boxes and the ground truths
+ * as queries; ign_det / ign_gt: -1 another class, 0 counts, 1 ignored; det_bbox [n_det, 4], dc_bbox / dc_off (DontCare
+ * regions per frame) are read for metric 0 only, the alphas only with compute_aos.
+ * toda_eval_match_scores: the threshold-free first pass: scores_out[gt_off[f] + k], k < count_out[f], are the scores of the
+ * detections matched to frame f's counted ground truths, in ground-truth order.
+ * ws: toda_eval_match_workspace_bytes(n_frames, n_thresh, n_det_total) bytes (n_thresh = 1 for _scores).
+ * ---------------------------------------------------------------------- */
+int toda_eval_overlaps(const float* box3d, const float* bbox, const int32_t* box_off, const float* query3d,
+                       const float* query_bbox, const int32_t* query_off, const long long* out_off, int n_frames,
+                       long long n_pairs, int metric, int criterion, float* out, void* stream);
+size_t toda_eval_match_workspace_bytes(int n_frames, int n_thresh, int n_det_total);
+int toda_eval_match_scores(const float* overlaps, const long long* ov_off, const int32_t* det_off, const int32_t* gt_off,
+                           const int32_t* ign_det, const int32_t* ign_gt, const double* det_score, int n_frames,
+                           int n_det_total, double min_overlap, double* scores_out, int32_t* count_out, void* ws,
+                           size_t ws_bytes, void* stream);
+int toda_eval_match(const float* overlaps, const long long* ov_off, const int32_t* det_off, const int32_t* gt_off,
+                    const int32_t* ign_det, const int32_t* ign_gt, const double* det_score, const double* det_alpha,
+                    const double* gt_alpha, const double* det_bbox, const double* dc_bbox, const int32_t* dc_off, int n_frames,
+                    int n_det_total, const double* thresholds, int n_thresh, double min_overlap, int metric, int compute_aos,
+                    double* pr, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -151,6 +151,10 @@ SIGNATURES = {
     "toda_center_assign": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _dbl, _i, _vp, _vp, _vp, _vp, _vp]),
     "toda_anchor_assign_workspace_bytes": (_sz, [_i, _i]),
     "toda_anchor_assign": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "toda_eval_overlaps": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_longlong, _i, _i, _vp, _vp]),
+    "toda_eval_match_workspace_bytes": (_sz, [_i, _i, _i]),
+    "toda_eval_match_scores": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _dbl, _vp, _vp, _vp, _sz, _vp]),
+    "toda_eval_match": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _dbl, _i, _i, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

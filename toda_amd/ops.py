@@ -1765,6 +1765,86 @@ def anchor_assign(anchors, gt_boxes, slot_of, matched, unmatched, code_size, enc
     return labels, targets, weights
 
 
+def _eval_arg(t, dtype, what):
+    if t is None:
+        return None
+    if not t.is_cuda:
+        raise RuntimeError("toda_amd ops need tensors on the GPU (there is no CPU path)")
+    if t.dtype != dtype or not t.is_contiguous():
+        raise RuntimeError(f"{what} must be a contiguous {dtype} tensor")
+    return t
+
+
+def eval_overlaps(box3d, bbox, box_off, query3d, query_bbox, query_off, out_off, n_pairs, metric, criterion=-1):
+    """The KITTI evaluator's per-frame overlaps (toda_eval_overlaps): flat fp32 of n_pairs values, frame f's
+    [n_box_f, n_query_f] block at out_off[f].  box3d / query3d [N, 7] = x, y, z, l, h, w, rotation_y (camera frame), bbox /
+    query_bbox [N, 4]; box_off / query_off int32 [F + 1], out_off int64 [F + 1].  metric 0 image box, 1 BEV, 2 3-D."""
+    box_off, query_off = _eval_arg(box_off, torch.int32, "eval_overlaps: box_off"), _eval_arg(query_off, torch.int32, "eval_overlaps: query_off")
+    out_off = _eval_arg(out_off, torch.int64, "eval_overlaps: out_off")
+    boxes = [_eval_arg(t, torch.float32, "eval_overlaps: boxes") for t in (box3d, bbox, query3d, query_bbox)]
+    n_frames = int(box_off.numel()) - 1
+    if query_off.numel() != n_frames + 1 or out_off.numel() != n_frames + 1:
+        raise RuntimeError("eval_overlaps: the three offset arrays must have one length")
+    out = torch.empty((int(n_pairs),), dtype=torch.float32, device=box_off.device)
+    rc = L.load().toda_eval_overlaps(L.ptr(boxes[0]), L.ptr(boxes[1]), L.ptr(box_off), L.ptr(boxes[2]), L.ptr(boxes[3]),
+                                     L.ptr(query_off), L.ptr(out_off), n_frames, int(n_pairs), int(metric), int(criterion),
+                                     L.ptr(out), L.stream())
+    L.check(rc, "toda_eval_overlaps")
+    return out
+
+
+def _eval_match_common(overlaps, ov_off, det_off, gt_off, ign_det, ign_gt, score, who):
+    overlaps = _eval_arg(overlaps, torch.float32, f"{who}: overlaps")
+    ov_off = _eval_arg(ov_off, torch.int64, f"{who}: ov_off")
+    offs = [_eval_arg(t, torch.int32, f"{who}: offsets and flags") for t in (det_off, gt_off, ign_det, ign_gt)]
+    score = _eval_arg(score, torch.float64, f"{who}: score")
+    n_frames = int(offs[0].numel()) - 1
+    n_det, n_gt = int(offs[2].numel()), int(offs[3].numel())
+    if offs[1].numel() != n_frames + 1 or ov_off.numel() != n_frames + 1 or score.numel() != n_det:
+        raise RuntimeError(f"{who}: offsets need one length, and one score per detection flag")
+    return overlaps, ov_off, offs, score, n_frames, n_det, n_gt
+
+
+def eval_match_scores(overlaps, ov_off, det_off, gt_off, ign_det, ign_gt, score, min_overlap):
+    """The evaluator's threshold-free matching pass (toda_eval_match_scores) -> (scores fp64 [n_gt], counts int32 [F]): the
+    first counts[f] entries from gt_off[f] on are the scores of the detections matched to frame f's counted ground truths."""
+    lib = L.load()
+    overlaps, ov_off, offs, score, n_frames, n_det, n_gt = _eval_match_common(overlaps, ov_off, det_off, gt_off, ign_det, ign_gt,
+                                                                              score, "eval_match_scores")
+    dev = ov_off.device
+    scores_out = torch.empty((n_gt,), dtype=torch.float64, device=dev)
+    counts = torch.zeros((max(n_frames, 0),), dtype=torch.int32, device=dev)
+    ws_bytes = lib.toda_eval_match_workspace_bytes(n_frames, 1, n_det)
+    ws = torch.empty((max(int(ws_bytes), 1),), dtype=torch.uint8, device=dev)
+    rc = lib.toda_eval_match_scores(L.ptr(overlaps), L.ptr(ov_off), L.ptr(offs[0]), L.ptr(offs[1]), L.ptr(offs[2]), L.ptr(offs[3]),
+                                    L.ptr(score), n_frames, n_det, float(min_overlap), L.ptr(scores_out), L.ptr(counts),
+                                    L.ptr(ws), ws_bytes, L.stream())
+    L.check(rc, "toda_eval_match_scores")
+    return scores_out, counts
+
+
+def eval_match(overlaps, ov_off, det_off, gt_off, ign_det, ign_gt, score, det_alpha, gt_alpha, det_bbox, dc_bbox, dc_off,
+               thresholds, min_overlap, metric, compute_aos=False):
+    """The evaluator's matching at every score threshold (toda_eval_match) -> pr fp64 [T, 4] = (tp, fp, fn, AOS similarity)
+    summed over the frames in a fixed order.  det_bbox / dc_bbox / dc_off are read for metric 0, the alphas with compute_aos."""
+    lib = L.load()
+    overlaps, ov_off, offs, score, n_frames, n_det, n_gt = _eval_match_common(overlaps, ov_off, det_off, gt_off, ign_det, ign_gt,
+                                                                              score, "eval_match")
+    f64 = [_eval_arg(t, torch.float64, "eval_match: alphas, image boxes and thresholds") for t in (det_alpha, gt_alpha, det_bbox, dc_bbox, thresholds)]
+    dc_off = _eval_arg(dc_off, torch.int32, "eval_match: dc_off")
+    dev = ov_off.device
+    n_thresh = int(f64[4].numel())
+    pr = torch.zeros((n_thresh, 4), dtype=torch.float64, device=dev)
+    ws_bytes = lib.toda_eval_match_workspace_bytes(n_frames, n_thresh, n_det)
+    ws = torch.empty((max(int(ws_bytes), 1),), dtype=torch.uint8, device=dev)
+    rc = lib.toda_eval_match(L.ptr(overlaps), L.ptr(ov_off), L.ptr(offs[0]), L.ptr(offs[1]), L.ptr(offs[2]), L.ptr(offs[3]),
+                             L.ptr(score), L.ptr(f64[0]), L.ptr(f64[1]), L.ptr(f64[2]), L.ptr(f64[3]), L.ptr(dc_off), n_frames,
+                             n_det, L.ptr(f64[4]), n_thresh, float(min_overlap), int(metric), int(bool(compute_aos)), L.ptr(pr),
+                             L.ptr(ws), ws_bytes, L.stream())
+    L.check(rc, "toda_eval_match")
+    return pr
+
+
 class _CenterLoss(torch.autograd.Function):
     """CenterHead.get_loss of one head group in three launches forward / one backward (toda_center_loss_*).
     apply(n, hm_logits, reg_0..reg_{n-1}, heatmap, inds, mask, target_boxes, code_weights, cls_weight, loc_weight)

@@ -89,8 +89,9 @@ class DatasetTemplate(torch_data.Dataset):
         return annos
 
     def evaluation(self, det_annos, class_names, **kwargs):
-        """Dataset-specific metrics (KITTI / nuScenes / Waymo evaluators) are out of scope; a dataset with ground truth
-        in `self.infos` reports BEV-centre-distance recall / precision here."""
+        """A dataset with ground truth in `self.infos` reports here: the KITTI AP table for eval_metric "kitti"
+        (datasets/kitti/kitti_object_eval_python; the nuScenes / Waymo evaluators are out of scope), else BEV-centre-distance
+        recall / precision."""
         return "", {}
 
     @staticmethod

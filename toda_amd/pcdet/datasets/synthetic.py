@@ -109,9 +109,39 @@ class SyntheticLidarDataset(DatasetTemplate):
         with open(path, "wb") as f:
             pickle.dump(self.infos, f)
 
+    def kitti_eval(self, det_annos, class_names):
+        """KITTI AP through the LiDAR-frame route of the camera-less datasets (reference nuscenes_dataset.py kitti_eval):
+        deep copies of the predictions and of the frames' infos, class names mapped by DATA_CONFIG.MAP_CLASS_TO_KITTI
+        (unmapped ones become Person_sitting), then kitti_object_eval_python.get_official_eval_result."""
+        import copy
+
+        from .kitti import kitti_utils
+        from .kitti.kitti_object_eval_python import eval as kitti_eval
+        mapping = dict(self.dataset_cfg.get("MAP_CLASS_TO_KITTI", None) or {})
+        gt_by_frame = {Path(i["lidar_path"]).stem: i for i in self.infos}
+        eval_det_annos = copy.deepcopy(list(det_annos))
+        eval_gt_annos = []
+        for anno in eval_det_annos:
+            info = gt_by_frame[str(anno["frame_id"])]
+            eval_gt_annos.append({"name": np.array(info["gt_names"], dtype=object),
+                                  "gt_boxes_lidar": np.asarray(info["gt_boxes"], np.float64).reshape(-1, 7).copy()})
+            anno["name"] = np.array(anno["name"], dtype=object)
+            anno["boxes_lidar"] = np.asarray(anno["boxes_lidar"], np.float64).reshape(-1, 7)
+        full = {}
+        for annos in (eval_det_annos, eval_gt_annos):
+            for anno in annos:
+                for n in anno["name"]:
+                    full[n] = mapping.get(n, "Person_sitting")
+        kitti_utils.transform_annotations_to_kitti_format(eval_det_annos, map_name_to_kitti=full)
+        kitti_utils.transform_annotations_to_kitti_format(eval_gt_annos, map_name_to_kitti=full)
+        kitti_class_names = [mapping.get(c, "Person_sitting") for c in class_names]
+        return kitti_eval.get_official_eval_result(eval_gt_annos, eval_det_annos, kitti_class_names)
+
     def evaluation(self, det_annos, class_names, **kwargs):
-        """Centre-distance matching (<= 2 m in BEV, greedy by score) of predictions against the frames' boxes ->
-        recall / precision per class.  Stands in for the KITTI / nuScenes evaluators (out of scope)."""
+        """eval_metric == "kitti": the KITTI AP table (kitti_eval above).  Any other value: centre-distance matching
+        (<= 2 m in BEV, greedy by score) of predictions against the frames' boxes -> recall / precision per class."""
+        if kwargs.get("eval_metric", None) == "kitti":
+            return self.kitti_eval(det_annos, class_names)
         gt_by_frame = {Path(i["lidar_path"]).stem: i for i in self.infos}
         tp = {c: 0 for c in class_names}
         n_gt, n_det = dict(tp), dict(tp)
