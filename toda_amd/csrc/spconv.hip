@@ -155,24 +155,17 @@ struct GatherClasses {
     unsigned char k[8][27];       // ascending kernel-offset indices
 };
 
-// PF = software pipeline depth: with PF the neighbour ids of offset k+2 and the gathered rows of
-// offset k+1 are requested before the MFMAs of offset k issue, so a wave's HBM/L2 round trips run
-// under its own matrix work instead of relying on other waves to cover them.
-template <int Q, int NT, int RT, bool PF, bool VEC, bool CLS = false>
+// One offset at a time: ids -> wave-uniform skip -> gather -> MFMAs; the round trips of a wave are covered by the other waves of the
+// SIMD (the software-pipelined form of this loop and a contiguous-range-per-XCD tile order were tried and retired:
+// profiles/EXPERIMENTS.md, "Variants retired from the gather-GEMM kernels").
+template <int Q, int NT, int RT, bool VEC, bool CLS = false>
 __global__ void __launch_bounds__(SC_BLOCK)
 gather_gemm_kernel(const float* __restrict__ in, int n_in, int cg, const float* __restrict__ wp,
                    const int* __restrict__ nbr, int n_out, int K, int cp, const float* __restrict__ bias,
-                   float* __restrict__ out, int xcd_order, const int* __restrict__ order,
+                   float* __restrict__ out, const int* __restrict__ order,
                    const unsigned char* __restrict__ cls_sorted, const GatherClasses classes) {
     const int lane = threadIdx.x & 63;
-    // XCD-aware tile order: workgroups are dealt round-robin over the 8 XCDs (private L2s), so give
-    // each XCD one contiguous range of row tiles - canonical rows are spatial neighbours and gather
-    // overlapping input rows, which then hit in that XCD's L2 instead of being fetched 8 times.
-    // (speed only; any placement is correct)
-    const int nwg = gridDim.x, xcd = blockIdx.x & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const int tile_block = xcd_order ? (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3)
-                                     : (int)blockIdx.x;
-    const int wave = tile_block * (SC_BLOCK / 64) + (threadIdx.x >> 6);
+    const int wave = (int)blockIdx.x * (SC_BLOCK / 64) + (threadIdx.x >> 6);
     const int r = lane & 15, g = lane >> 4;
     const int row0 = wave * (16 * RT);
     if (row0 >= n_out) return;  // wave-uniform
@@ -239,65 +232,38 @@ gather_gemm_kernel(const float* __restrict__ in, int n_in, int cg, const float* 
         }
     };
 
-    if constexpr (PF) {
-        int s0[RT], s1[RT], s2[RT];
-        f32x4 a0[RT][Q], a1[RT][Q];
-        load_ids(0, s0);
-        load_ids(1, s1);
-        gather_rows<Q, RT, VEC>(in_rsrc, cg, g, s0, a0);
-        for (int k = 0; k < K; ++k) {
-            load_ids(k + 2, s2);
-            gather_rows<Q, RT, VEC>(in_rsrc, cg, g, s1, a1);  // rows of offset k+1, in flight during the MFMAs below
-            bool hit[RT];
-            bool any = false;
+    auto offset = [&](int k) {
+        int src[RT];
+        load_ids(k, src);
+        bool hit[RT];
+        bool any = false;
 #pragma unroll
-            for (int rt = 0; rt < RT; ++rt) {
-                hit[rt] = __any(s0[rt] >= 0);
-                any = any || hit[rt];
-            }
-            if (any) mma(k, a0, hit);
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt) {
-                s0[rt] = s1[rt];
-                s1[rt] = s2[rt];
-#pragma unroll
-                for (int q = 0; q < Q; ++q) a0[rt][q] = a1[rt][q];
-            }
+        for (int rt = 0; rt < RT; ++rt) {
+            hit[rt] = __any(src[rt] >= 0);
+            any = any || hit[rt];
         }
+        if (!any) return;  // wave-uniform skip of an empty offset
+        f32x4 a[RT][Q];
+        gather_rows<Q, RT, VEC>(in_rsrc, cg, g, src, a);
+        mma(k, a, hit);
+    };
+    // CLS (separate instantiation, so that the plain kernel compiles as it always did): class of this wave's rows (positions
+    // row0 .. row0 + 16 RT - 1 of the class-sorted order); if they all agree the wave walks that class's offset list only
+    const unsigned char* klist = nullptr;
+    int n_k = 0;
+    if constexpr (CLS) {
+        const int p = row0 + (lane & (16 * RT - 1) & 63);
+        const int c = cls_sorted[p < n_out ? p : n_out - 1];
+        const int c0 = __builtin_amdgcn_readfirstlane(c);
+        if (__all(c == c0 || p >= n_out) && classes.count[c0 & 7] > 0) {
+            klist = classes.k[c0 & 7];
+            n_k = classes.count[c0 & 7];
+        }
+    }
+    if (CLS && klist) {
+        for (int t = 0; t < n_k; ++t) offset(klist[t]);
     } else {
-        auto offset = [&](int k) {
-            int src[RT];
-            load_ids(k, src);
-            bool hit[RT];
-            bool any = false;
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt) {
-                hit[rt] = __any(src[rt] >= 0);
-                any = any || hit[rt];
-            }
-            if (!any) return;  // wave-uniform skip of an empty offset
-            f32x4 a[RT][Q];
-            gather_rows<Q, RT, VEC>(in_rsrc, cg, g, src, a);
-            mma(k, a, hit);
-        };
-        // CLS (separate instantiation, so that the plain kernel compiles as it always did): class of this wave's rows (positions
-        // row0 .. row0 + 16 RT - 1 of the class-sorted order); if they all agree the wave walks that class's offset list only
-        const unsigned char* klist = nullptr;
-        int n_k = 0;
-        if constexpr (CLS) {
-            const int p = row0 + (lane & (16 * RT - 1) & 63);
-            const int c = cls_sorted[p < n_out ? p : n_out - 1];
-            const int c0 = __builtin_amdgcn_readfirstlane(c);
-            if (__all(c == c0 || p >= n_out) && classes.count[c0 & 7] > 0) {
-                klist = classes.k[c0 & 7];
-                n_k = classes.count[c0 & 7];
-            }
-        }
-        if (CLS && klist) {
-            for (int t = 0; t < n_k; ++t) offset(klist[t]);
-        } else {
-            for (int k = 0; k < K; ++k) offset(k);
-        }
+        for (int k = 0; k < K; ++k) offset(k);
     }
 
     const bool full = cp == 16 * NT;
@@ -364,8 +330,8 @@ __device__ __forceinline__ int xcd_chunked_block(int b, int nblk) {
 // streaming it through L1 (4x less vector-memory traffic: with per-wave weight loads the CU's
 // 64 B/clk L1 path, not the MFMA pipe, sets the pace - measured 59 % matrix-pipe utilisation).
 // One barrier per offset; waves still skip the MFMAs of offsets without a neighbour in their rows.
-template <int Q, int NT, int RT, bool VEC, bool DB = true, int BLK = SC_BLOCK, bool PFL = false, bool IDPF = false>
-__global__ void __launch_bounds__(BLK, PFL ? 3 : (Q * NT <= 4 && RT <= 2) ? GG_LDS_WAVES_NARROW : (Q * NT * RT <= 32 && Q * NT <= 16) ? GG_LDS_WAVES : (BLK > SC_BLOCK ? GG_LDS_WAVES_WIDE : 1))
+template <int Q, int NT, int RT, bool VEC, bool DB = true, int BLK = SC_BLOCK, bool IDPF = false>
+__global__ void __launch_bounds__(BLK, (Q * NT <= 4 && RT <= 2) ? GG_LDS_WAVES_NARROW : (Q * NT * RT <= 32 && Q * NT <= 16) ? GG_LDS_WAVES : (BLK > SC_BLOCK ? GG_LDS_WAVES_WIDE : 1))
 gather_gemm_lds_kernel(const float* __restrict__ in, int n_in, int cg, const float* __restrict__ wp,
                        const int* __restrict__ nbr, int n_out, int K, int cp, const float* __restrict__ bias,
                        float* __restrict__ out, const int* __restrict__ order, double* __restrict__ stats) {
@@ -403,157 +369,84 @@ gather_gemm_lds_kernel(const float* __restrict__ in, int n_in, int cg, const flo
         if (e < SLICE) wl[0][e] = wp4[e];
     }
     __syncthreads();
-
-    if constexpr (PFL) {
-        // software-pipelined variant (experiment): neighbour ids two offsets ahead, gathered rows one offset ahead, in two
-        // register sets that alternate (loop body written twice: no register copies - vector moves cost matrix time here)
-        static_assert(DB, "pipelined variant needs the double-buffered weight slices");
-        auto load_ids = [&](int k, int (&dst)[RT]) {
-            const int kk = k < K ? k : K - 1;
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt) {
-                const int v = nbr[(size_t)kk * n_out + rows[rt]];
-                dst[rt] = (k < K && live[rt]) ? v : -1;
-            }
-        };
-        auto body = [&](int k, const int (&s_cur)[RT], const f32x4 (&a_cur)[RT][Q], int (&s_ids)[RT], const int (&s_next)[RT], f32x4 (&a_next)[RT][Q]) {
-            const int cur = k & 1;
-            f32x4 stage[PER_THREAD];
-            if (k + 1 < K) {
-#pragma unroll
-                for (int t = 0; t < PER_THREAD; ++t) {
-                    const int e = t * BLK + threadIdx.x;
-                    if (e < SLICE) stage[t] = wp4[(size_t)(k + 1) * SLICE + e];
-                }
-            }
-            load_ids(k + 2, s_ids);                                   // overwrites the ids of offset k - 1 (dead)
-            gather_rows<Q, RT, VEC>(in_rsrc, cg, g, s_next, a_next);   // rows of offset k + 1, in flight under the MFMAs below
-            bool hit[RT];
-            bool any = false;
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt) {
-                hit[rt] = __any(s_cur[rt] >= 0);
-                any = any || hit[rt];
-            }
-            if (any) {
-#pragma unroll
-                for (int q = 0; q < Q; ++q) {
-                    f32x4 b[NT];
-#pragma unroll
-                    for (int n = 0; n < NT; ++n) b[n] = wl[cur][(q * NT + n) * 64 + lane];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-#pragma unroll
-                        for (int n = 0; n < NT; ++n)
-#pragma unroll
-                            for (int rt = 0; rt < RT; ++rt)
-                                if (hit[rt]) acc[rt][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_cur[rt][q][j], b[n][j], acc[rt][n], 0, 0, 0);
-                }
-            }
-            if (k + 1 < K) {
-#pragma unroll
-                for (int t = 0; t < PER_THREAD; ++t) {
-                    const int e = t * BLK + threadIdx.x;
-                    if (e < SLICE) wl[cur ^ 1][e] = stage[t];
-                }
-            }
-            __syncthreads();
-        };
-        int sA[RT], sB[RT], sC[RT];
-        f32x4 aA[RT][Q], aB[RT][Q];
-        load_ids(0, sA);
-        load_ids(1, sB);
-        gather_rows<Q, RT, VEC>(in_rsrc, cg, g, sA, aA);
-        // ids rotate through three sets (period 3), rows through two (period 2): six offsets per trip
-        int k = 0;
-        while (true) {
-            body(k, sA, aA, sC, sB, aB); if (++k >= K) break;      // cur ids A, next ids B, k+2 -> C
-            body(k, sB, aB, sA, sC, aA); if (++k >= K) break;
-            body(k, sC, aA, sB, sA, aB); if (++k >= K) break;
-            body(k, sA, aB, sC, sB, aA); if (++k >= K) break;
-            body(k, sB, aA, sA, sC, aB); if (++k >= K) break;
-            body(k, sC, aB, sB, sA, aA); if (++k >= K) break;
-        }
-    } else {
     int id_next[RT];
     if constexpr (IDPF) {
-    #pragma unroll
+#pragma unroll
         for (int rt = 0; rt < RT; ++rt) id_next[rt] = __builtin_nontemporal_load(nbr + rows[rt]);
     }
     for (int k = 0; k < K; ++k) {
-            const int cur = DB ? (k & 1) : 0;
-            // this offset's neighbour ids FIRST in program order: vmcnt counts in issue order, so a wait for ids that were issued
-            // behind the weight loads below would also wait for those (they are not needed before the end of the offset)
-            int src[RT];
-            if constexpr (IDPF) {
-                // ids one offset ahead (<= 64-channel variants with two row tiles per wave): the id -> row -> MFMA chain of an offset
-                // loses its first memory round trip.  Worth 1-4 % (32 -> 32 @ 682k rows 0.307 -> 0.303 ms, 32 -> 64 0.299 -> 0.288,
-                // 64 -> 64 0.589 -> 0.584): the chain is not what holds the matrix pipe at 62-69 %
-                const int kn = k + 1 < K ? k + 1 : K - 1;
-    #pragma unroll
-                for (int rt = 0; rt < RT; ++rt) {
-                    src[rt] = live[rt] ? id_next[rt] : -1;
-                    id_next[rt] = __builtin_nontemporal_load(nbr + (size_t)kn * n_out + rows[rt]);
-                }
-            } else {
-    #pragma unroll
+        const int cur = DB ? (k & 1) : 0;
+        // this offset's neighbour ids FIRST in program order: vmcnt counts in issue order, so a wait for ids that were issued
+        // behind the weight loads below would also wait for those (they are not needed before the end of the offset)
+        int src[RT];
+        if constexpr (IDPF) {
+            // ids one offset ahead (<= 64-channel variants with two row tiles per wave): the id -> row -> MFMA chain of an offset
+            // loses its first memory round trip.  Worth 1-4 % (32 -> 32 @ 682k rows 0.307 -> 0.303 ms, 32 -> 64 0.299 -> 0.288,
+            // 64 -> 64 0.589 -> 0.584): the chain is not what holds the matrix pipe at 62-69 %
+            const int kn = k + 1 < K ? k + 1 : K - 1;
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt) {
+                src[rt] = live[rt] ? id_next[rt] : -1;
+                id_next[rt] = __builtin_nontemporal_load(nbr + (size_t)kn * n_out + rows[rt]);
+            }
+        } else {
+#pragma unroll
             for (int rt = 0; rt < RT; ++rt) {
                 const int v = __builtin_nontemporal_load(nbr + (size_t)k * n_out + rows[rt]);
                 src[rt] = live[rt] ? v : -1;
             }
+        }
+        asm volatile("" ::: "memory");      // keep the id loads in front of the weight loads
+        // next offset's weights: global -> registers now, registers -> LDS after this offset's math
+        // (unconditional: on the last offset the slice of offset K - 1 is fetched again and dropped - a branch around the loads
+        // makes the compiler's wait for the ids a wait for everything, see the note on wgrad_kernel's EXACT)
+        f32x4 stage[PER_THREAD];
+        {
+            const int kn = k + 1 < K ? k + 1 : K - 1;
+#pragma unroll
+            for (int t = 0; t < PER_THREAD; ++t) {
+                const int e = t * BLK + threadIdx.x;
+                if (SLICE % BLK == 0 || e < SLICE) stage[t] = wp4[(size_t)kn * SLICE + e];
             }
-            asm volatile("" ::: "memory");      // keep the id loads in front of the weight loads
-            // next offset's weights: global -> registers now, registers -> LDS after this offset's math
-            // (unconditional: on the last offset the slice of offset K - 1 is fetched again and dropped - a branch around the loads
-            // makes the compiler's wait for the ids a wait for everything, see the note on wgrad_kernel's EXACT)
-            f32x4 stage[PER_THREAD];
-            {
-                const int kn = k + 1 < K ? k + 1 : K - 1;
-    #pragma unroll
-                for (int t = 0; t < PER_THREAD; ++t) {
-                    const int e = t * BLK + threadIdx.x;
-                    if (SLICE % BLK == 0 || e < SLICE) stage[t] = wp4[(size_t)kn * SLICE + e];
-                }
-            }
-            bool hit[RT];
-            bool any = false;
-    #pragma unroll
-            for (int rt = 0; rt < RT; ++rt) {
-                hit[rt] = __any(src[rt] >= 0);
-                any = any || hit[rt];
-            }
-            if (any) {
-                f32x4 a[RT][Q];
-                gather_rows<Q, RT, VEC>(in_rsrc, cg, g, src, a);
-    #pragma unroll
-                for (int q = 0; q < Q; ++q) {
-                    f32x4 b[NT];
-    #pragma unroll
-                    for (int n = 0; n < NT; ++n) b[n] = wl[cur][(q * NT + n) * 64 + lane];
-    #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-    #pragma unroll
-                        for (int n = 0; n < NT; ++n) {
-    #pragma unroll
-                            for (int rt = 0; rt < RT; ++rt) {
-                                if (hit[rt])
-                                    acc[rt][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[rt][q][j], b[n][j], acc[rt][n], 0, 0, 0);
-                            }
+        }
+        bool hit[RT];
+        bool any = false;
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) {
+            hit[rt] = __any(src[rt] >= 0);
+            any = any || hit[rt];
+        }
+        if (any) {
+            f32x4 a[RT][Q];
+            gather_rows<Q, RT, VEC>(in_rsrc, cg, g, src, a);
+#pragma unroll
+            for (int q = 0; q < Q; ++q) {
+                f32x4 b[NT];
+#pragma unroll
+                for (int n = 0; n < NT; ++n) b[n] = wl[cur][(q * NT + n) * 64 + lane];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+#pragma unroll
+                    for (int n = 0; n < NT; ++n) {
+#pragma unroll
+                        for (int rt = 0; rt < RT; ++rt) {
+                            if (hit[rt])
+                                acc[rt][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[rt][q][j], b[n][j], acc[rt][n], 0, 0, 0);
                         }
                     }
                 }
             }
-            if (!DB) __syncthreads();  // everyone is done reading the single buffer
-            if (k + 1 < K) {
-    #pragma unroll
-                for (int t = 0; t < PER_THREAD; ++t) {
-                    const int e = t * BLK + threadIdx.x;
-                    if (e < SLICE) wl[DB ? (cur ^ 1) : 0][e] = stage[t];
-                }
-            }
-            __syncthreads();
         }
-}
+        if (!DB) __syncthreads();  // everyone is done reading the single buffer
+        if (k + 1 < K) {
+#pragma unroll
+            for (int t = 0; t < PER_THREAD; ++t) {
+                const int e = t * BLK + threadIdx.x;
+                if (e < SLICE) wl[DB ? (cur ^ 1) : 0][e] = stage[t];
+            }
+        }
+        __syncthreads();
+    }
     if (row0 >= n_out && !stats) return;
 
     // BatchNorm statistics of the layer's output, taken from the accumulators (reference spconv_backbone.py:21-25: every conv
@@ -1328,25 +1221,6 @@ extern "C" int toda_spconv_pack_weights(int n, const float* const* w, const int3
     return sflush();
 }
 
-namespace toda {
-__global__ void fold_partials_kernel(double* __restrict__ sums, int blocks, int cols);   // dense.hip
-}
-// The per-workgroup BatchNorm partials of a statistics launch are folded right away (fold_partials_kernel), or - for
-// toda_spconv_gather_gemm_stats_partials - left for toda_bn_finalize_partials, which folds and finalises in one launch; the entry
-// point then reports the number of partials per column through this (thread-local: the call is synchronous on the host) slot.
-static thread_local int* g_stats_blocks_out = nullptr;
-static void fold_or_defer(double* stats, int blocks, int c_produce, hipStream_t s) {
-    if (g_stats_blocks_out) {
-        *g_stats_blocks_out = blocks;
-        return;
-    }
-    hipLaunchKernelGGL(toda::fold_partials_kernel, dim3(2 * c_produce), dim3(256), 0, s, stats, blocks, 2 * c_produce);
-}
-
-static int gather_gemm_impl(const float* in, int n_in, int c_gather, const float* wp, const int32_t* nbr, int n_out, int k_vol,
-                            int c_produce, const float* bias, float* out, const int32_t* order, double* stats, void* stream,
-                            const unsigned char* cls_sorted = nullptr, const toda::GatherClasses* cls_table = nullptr);
-
 // ---- residue-class row order for the data gradient of strided convolutions (see GatherClasses) ------------------------------
 // Inside blocks of CLS_ROWS consecutive (spatially adjacent) rows the rows are regrouped by class with a stable counting sort:
 // one workgroup per block, a thread owns CLS_ROWS / 256 consecutive rows.
@@ -1441,17 +1315,6 @@ extern "C" int toda_rulebook_class_order(const int32_t* in_coords, int n_in, con
     return TODA_OK;
 }
 
-extern "C" int toda_spconv_gather_gemm_classed(const float* in, int n_in, int c_gather, const float* wp, const int32_t* nbr, int n_out, int k_vol,
-                                               int c_produce, const float* bias, float* out, const int32_t* order,
-                                               const unsigned char* cls_sorted, const int32_t* ksize, const int32_t* stride,
-                                               const int32_t* padding, void* stream) {
-    TODA_CHECK_ARG(order && cls_sorted && ksize && stride && padding, "gather_gemm_classed: null argument");
-    TODA_CHECK_ARG(ksize[0] * ksize[1] * ksize[2] == k_vol, "gather_gemm_classed: kernel size does not match the table's %d offsets", k_vol);
-    GatherClasses table;
-    TODA_CHECK_ARG(class_table(ksize, stride, padding, &table) == 0, "gather_gemm_classed: needs <= 8 residue classes and <= 27 offsets");
-    return gather_gemm_impl(in, n_in, c_gather, wp, nbr, n_out, k_vol, c_produce, bias, out, order, nullptr, stream, cls_sorted, &table);
-}
-
 // ---- optional per-launch timestamps of the gather-GEMM kernels -------------------------------
 // hipExtLaunchKernelGGL stamps a start / stop event pair on the kernel dispatch itself, so the
 // elapsed time is the kernel's own duration (what rocprofv3 --kernel-trace reports).  Events
@@ -1518,14 +1381,159 @@ static bool gg_stats_supported(int c_gather, int c_produce) {
     const int Q = tiles_pow2(c_gather), NT = tiles_pow2(c_produce);
     return (c_gather & 3) == 0 && Q >= 2 && NT >= Q && Q * NT <= 32 && !(Q == 8 && NT == 8) && c_produce % 4 == 0 && c_produce == 16 * NT;
 }
+
+// Run-time tile counts (1, 2, 4 or 8: tiles_pow2 of at most 128 channels) -> compile-time constants: f(tile_c<a>{}, tile_c<b>{}).
+template <int V>
+using tile_c = std::integral_constant<int, V>;
+template <class F>
+static void with_tiles(int tiles, F&& f) {
+    switch (tiles) {
+        case 1: f(tile_c<1>{}); break;
+        case 2: f(tile_c<2>{}); break;
+        case 4: f(tile_c<4>{}); break;
+        default: f(tile_c<8>{}); break;
+    }
+}
+template <class F>
+static void with_tiles(int a, int b, F&& f) {
+    with_tiles(a, [&](auto ta) { with_tiles(b, [&](auto tb) { f(ta, tb); }); });
+}
+
+// What one gather-GEMM launch runs.  In every family a wave owns 16 rt output rows and a workgroup is block / 64 waves, so `grid` is
+// also the number of per-workgroup partial sums a statistics launch writes.
+struct GatherRoute {
+    enum Family { SPLIT, LDS_128, LDS, REG } family;
+    int rt, block, grid;
+    bool vec;      // REG: rows are 16-byte aligned (16-byte gathers; the class-sorted kernel needs them)
+};
 }  // namespace toda
 
+static int gather_route(int c_gather, int c_produce, int n_out, bool stats, bool cls_sorted, GatherRoute* r) {
+    const int Q = tiles_pow2(c_gather), NT = tiles_pow2(c_produce);
+    const bool vec_ok = (c_gather & 3) == 0;
+    // weight staging: the LDS-shared slice when it measured faster (Q >= 2 and NT >= Q); TODA_GG_LDS = 0 never, 2 always
+    static const int env_lds_raw = getenv("TODA_GG_LDS") ? atoi(getenv("TODA_GG_LDS")) : 1;
+    const int env_lds = env_lds_raw == 2 ? 1 : (env_lds_raw == 1 ? (Q >= 2 && NT >= Q) : 0);
+    r->rt = 2, r->block = SC_BLOCK, r->vec = vec_ok;
+    if (use_split(c_gather, c_produce)) {     // matrix path "split": wp holds the three-plane bf16 operand (spconv_split.cuh)
+        TODA_CHECK_ARG(!(cls_sorted && stats), "gather_gemm (split path): no statistics on a class-sorted launch");
+        r->family = GatherRoute::SPLIT;
+    } else if (vec_ok && Q == 8 && NT == 8 && !cls_sorted) {
+        // 128 -> 128: one 64 KiB slice shared by a 512-thread workgroup, 16 rows per wave (0.67 ms against 0.76 for two row tiles per
+        // wave and 0.70 for register-only weights on 97.5k x 27 x 128 x 128)
+        r->family = GatherRoute::LDS_128, r->rt = 1, r->block = 512;
+    } else if ((env_lds || stats) && !cls_sorted && vec_ok && Q * NT <= 32) {  // weight slice <= 32 KiB per buffer
+        r->family = GatherRoute::LDS, r->rt = NT < 8 ? 2 : 1;
+    } else {
+        // register-resident weights (gather_gemm_kernel): the narrow, the "more gathered than produced" and the class-sorted launches;
+        // rows that are not 16-byte aligned (e.g. 5 point features) take dword gathers
+        TODA_CHECK_ARG(!stats, "gather_gemm: statistics requested on a launch shape without the fused epilogue");
+        TODA_CHECK_ARG(vec_ok || Q == 1, "gather_gemm: gathered channel counts above 16 must be multiples of 4 (got %d)", c_gather);
+        r->family = GatherRoute::REG;
+        r->rt = NT < 8 ? 2 : (Q < 8 ? 1 : 2);      // 128 -> 128: two row tiles measured 16 % faster than one
+    }
+    r->grid = cdiv(cdiv(n_out, 16 * r->rt), r->block / 64);
+    return TODA_OK;
+}
 
+// Every gather-GEMM entry point ends here.  stats (nullable): the BatchNorm partials of the launch ([2 c][workgroups] behind the 2 c result
+// slots) are folded right away (fold_partials_kernel) when blocks_out is null; otherwise they are left for toda_bn_finalize_partials, which
+// folds and finalises in one launch, and *blocks_out (host) = partials per column.
+static int gather_gemm_impl(const float* in, int n_in, int c_gather, const float* wp, const int32_t* nbr, int n_out, int k_vol,
+                            int c_produce, const float* bias, float* out, const int32_t* order, double* stats, int* blocks_out, void* stream,
+                            const unsigned char* cls_sorted = nullptr, const toda::GatherClasses* cls_table = nullptr) {
+    toda::GatherClasses classes = {};
+    if (cls_sorted && cls_table) classes = *cls_table;
+    else cls_sorted = nullptr;
+    TODA_CHECK_ARG(c_gather >= 1 && c_gather <= 128 && c_produce >= 1 && c_produce <= 128,
+                   "gather_gemm: channels must be in [1,128] (gather %d, produce %d)", c_gather, c_produce);
+    TODA_CHECK_ARG(n_out >= 0 && n_in >= 0 && k_vol >= 1, "gather_gemm: bad sizes");
+    TODA_CHECK_ARG((unsigned long long)n_in * c_gather * 4ull < 0xFFFFFFF0ull, "gather_gemm: gathered table must be < 4 GiB");
+    if (n_out == 0) return TODA_OK;
+    if (n_in == 0) {  // nothing to gather: bias only
+        TODA_CHECK_ARG(bias == nullptr, "gather_gemm: empty input with bias is unsupported");
+        TODA_HIP(hipMemsetAsync(out, 0, (size_t)n_out * c_produce * sizeof(float), (hipStream_t)stream));
+        return TODA_OK;
+    }
+    GatherRoute r;
+    const int rc = gather_route(c_gather, c_produce, n_out, stats != nullptr, cls_sorted != nullptr, &r);
+    if (rc != TODA_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(r.grid), block(r.block);
+    switch (r.family) {
+        case GatherRoute::SPLIT:
+            // one 32-channel chunk per stage; 32 produced channels: loads issued between the matrix groups; 128: three waves per SIMD
+            // (spconv_split.cuh has the numbers)
+            with_tiles(c_gather / 32, c_produce / 16, [&](auto kc, auto nt) {
+                constexpr int KC = decltype(kc)::value, NT = decltype(nt)::value;
+                if constexpr (KC <= 4 && NT >= 2)
+                    GG_LAUNCH(HIP_KERNEL_NAME(gg_split_kernel<KC, NT, (NT == 8 ? 3 : 4), (NT == 2)>), grid, block, 0, s, in, n_in,
+                              reinterpret_cast<const toda::u32x4*>(wp), nbr, n_out, k_vol, c_produce, bias, out, order, stats, cls_sorted, classes);
+            });
+            break;
+        case GatherRoute::LDS_128:
+            GG_LAUNCH(HIP_KERNEL_NAME(gather_gemm_lds_kernel<8, 8, 1, true, false, 512>), grid, block, 0, s, in, n_in, c_gather, wp, nbr, n_out,
+                      k_vol, c_produce, bias, out, order, stats);
+            break;
+        case GatherRoute::LDS:
+            with_tiles(tiles_pow2(c_gather), tiles_pow2(c_produce), [&](auto q, auto nt) {
+                constexpr int Q = decltype(q)::value, NT = decltype(nt)::value, RT = NT < 8 ? 2 : 1;
+                GG_LAUNCH(HIP_KERNEL_NAME(gather_gemm_lds_kernel<Q, NT, RT, true, true, SC_BLOCK, (Q <= 4 && NT <= 4 && RT == 2)>), grid, block, 0,
+                          s, in, n_in, c_gather, wp, nbr, n_out, k_vol, c_produce, bias, out, order, stats);
+            });
+            break;
+        case GatherRoute::REG: {
+            auto reg = [&](auto q, auto nt, auto rt, auto vec) {
+                constexpr int Q = decltype(q)::value, NT = decltype(nt)::value, RT = decltype(rt)::value;
+                constexpr bool VEC = decltype(vec)::value;
+                if (cls_sorted && VEC)
+                    GG_LAUNCH(HIP_KERNEL_NAME(gather_gemm_kernel<Q, NT, RT, true, true>), grid, block, 0, s, in, n_in, c_gather, wp, nbr, n_out,
+                              k_vol, c_produce, bias, out, order, cls_sorted, classes);
+                else
+                    GG_LAUNCH(HIP_KERNEL_NAME(gather_gemm_kernel<Q, NT, RT, VEC>), grid, block, 0, s, in, n_in, c_gather, wp, nbr, n_out, k_vol,
+                              c_produce, bias, out, order, nullptr, classes);
+            };
+            if (!r.vec) {
+                with_tiles(tiles_pow2(c_produce), [&](auto nt) {
+                    reg(tile_c<1>{}, nt, tile_c<(decltype(nt)::value < 8 ? 2 : 1)>{}, std::false_type{});
+                });
+            } else {
+                with_tiles(tiles_pow2(c_gather), tiles_pow2(c_produce), [&](auto q, auto nt) {
+                    if constexpr (decltype(nt)::value < 8) reg(q, nt, tile_c<2>{}, std::true_type{});
+                    else if (r.rt == 2) reg(q, nt, tile_c<2>{}, std::true_type{});
+                    else reg(q, nt, tile_c<1>{}, std::true_type{});
+                });
+            }
+            break;
+        }
+    }
+    TODA_LAUNCH_CHECK();
+    if (stats) {
+        if (blocks_out) {
+            *blocks_out = r.grid;
+        } else {
+            hipLaunchKernelGGL(toda::fold_partials_kernel, dim3(2 * c_produce), dim3(256), 0, s, stats, r.grid, 2 * c_produce);
+            TODA_LAUNCH_CHECK();
+        }
+    }
+    return TODA_OK;
+}
 
 extern "C" int toda_spconv_gather_gemm_ordered(const float* in, int n_in, int c_gather, const float* wp, const int32_t* nbr,
                                                int n_out, int k_vol, int c_produce, const float* bias, float* out,
                                                const int32_t* order, void* stream) {
-    return gather_gemm_impl(in, n_in, c_gather, wp, nbr, n_out, k_vol, c_produce, bias, out, order, nullptr, stream);
+    return gather_gemm_impl(in, n_in, c_gather, wp, nbr, n_out, k_vol, c_produce, bias, out, order, nullptr, nullptr, stream);
+}
+
+extern "C" int toda_spconv_gather_gemm_classed(const float* in, int n_in, int c_gather, const float* wp, const int32_t* nbr, int n_out, int k_vol,
+                                               int c_produce, const float* bias, float* out, const int32_t* order,
+                                               const unsigned char* cls_sorted, const int32_t* ksize, const int32_t* stride,
+                                               const int32_t* padding, void* stream) {
+    TODA_CHECK_ARG(order && cls_sorted && ksize && stride && padding, "gather_gemm_classed: null argument");
+    TODA_CHECK_ARG(ksize[0] * ksize[1] * ksize[2] == k_vol, "gather_gemm_classed: kernel size does not match the table's %d offsets", k_vol);
+    GatherClasses table;
+    TODA_CHECK_ARG(class_table(ksize, stride, padding, &table) == 0, "gather_gemm_classed: needs <= 8 residue classes and <= 27 offsets");
+    return gather_gemm_impl(in, n_in, c_gather, wp, nbr, n_out, k_vol, c_produce, bias, out, order, nullptr, nullptr, stream, cls_sorted, &table);
 }
 
 extern "C" int toda_spconv_gather_gemm_stats_supported(int c_gather, int c_produce) {
@@ -1542,7 +1550,7 @@ extern "C" int toda_spconv_gather_gemm_stats(const float* in, int n_in, int c_ga
     TODA_CHECK_ARG(sums != nullptr && gg_stats_supported(c_gather, c_produce) && n_out > 0 && n_in > 0,
                    "gather_gemm_stats: unsupported channel pair (%d -> %d) or empty table", c_gather, c_produce);
     TODA_CHECK_ARG(sums_doubles >= toda_spconv_gather_gemm_stats_doubles(n_out, c_produce), "gather_gemm_stats: statistics buffer too small");
-    return gather_gemm_impl(in, n_in, c_gather, wp, nbr, n_out, k_vol, c_produce, bias, out, nullptr, sums, stream);
+    return gather_gemm_impl(in, n_in, c_gather, wp, nbr, n_out, k_vol, c_produce, bias, out, nullptr, sums, nullptr, stream);
 }
 
 // The same launch without the fold: *blocks_out (host) = partial sums per column in the scratch behind the 2 c result slots, for
@@ -1554,143 +1562,12 @@ extern "C" int toda_spconv_gather_gemm_stats_partials(const float* in, int n_in,
                    "gather_gemm_stats_partials: unsupported channel pair (%d -> %d), empty table or null argument", c_gather, c_produce);
     TODA_CHECK_ARG(sums_doubles >= toda_spconv_gather_gemm_stats_doubles(n_out, c_produce), "gather_gemm_stats_partials: statistics buffer too small");
     *blocks_out = 0;
-    g_stats_blocks_out = blocks_out;
-    const int rc = gather_gemm_impl(in, n_in, c_gather, wp, nbr, n_out, k_vol, c_produce, bias, out, nullptr, sums, stream);
-    g_stats_blocks_out = nullptr;
+    const int rc = gather_gemm_impl(in, n_in, c_gather, wp, nbr, n_out, k_vol, c_produce, bias, out, nullptr, sums, blocks_out, stream);
     if (rc == TODA_OK && *blocks_out <= 0) {
         set_error("gather_gemm_stats_partials: the launch took no statistics");
         return TODA_EINVAL;
     }
     return rc;
-}
-
-
-static int gather_gemm_impl(const float* in, int n_in, int c_gather, const float* wp, const int32_t* nbr, int n_out, int k_vol,
-                            int c_produce, const float* bias, float* out, const int32_t* order, double* stats, void* stream,
-                            const unsigned char* cls_sorted, const toda::GatherClasses* cls_table) {
-    toda::GatherClasses classes = {};
-    if (cls_sorted && cls_table) classes = *cls_table;
-    else cls_sorted = nullptr;
-    TODA_CHECK_ARG(c_gather >= 1 && c_gather <= 128 && c_produce >= 1 && c_produce <= 128,
-                   "gather_gemm: channels must be in [1,128] (gather %d, produce %d)", c_gather, c_produce);
-    TODA_CHECK_ARG(n_out >= 0 && n_in >= 0 && k_vol >= 1, "gather_gemm: bad sizes");
-    TODA_CHECK_ARG((unsigned long long)n_in * c_gather * 4ull < 0xFFFFFFF0ull, "gather_gemm: gathered table must be < 4 GiB");
-    if (n_out == 0) return TODA_OK;
-    if (n_in == 0) {  // nothing to gather: bias only
-        TODA_CHECK_ARG(bias == nullptr, "gather_gemm: empty input with bias is unsupported");
-        TODA_HIP(hipMemsetAsync(out, 0, (size_t)n_out * c_produce * sizeof(float), (hipStream_t)stream));
-        return TODA_OK;
-    }
-    const int Q = tiles_pow2(c_gather), NT = tiles_pow2(c_produce);
-    hipStream_t s = (hipStream_t)stream;
-    const bool vec_ok = (c_gather & 3) == 0;
-    // weight staging: the LDS-shared slice when it measured faster (Q >= 2 and NT >= Q); TODA_GG_LDS = 0 never, 2 always
-    static const int env_lds_raw = getenv("TODA_GG_LDS") ? atoi(getenv("TODA_GG_LDS")) : 1;
-    const int env_lds = env_lds_raw == 2 ? 1 : (env_lds_raw == 1 ? (Q >= 2 && NT >= Q) : 0);
-    if (use_split(c_gather, c_produce)) {     // matrix path "split": wp holds the three-plane bf16 operand (spconv_split.cuh)
-        TODA_CHECK_ARG(k_vol >= 1 && !(cls_sorted && stats), "gather_gemm (split path): no statistics on a class-sorted launch");
-        const toda::u32x4* wps = reinterpret_cast<const toda::u32x4*>(wp);
-#define SPL(KK, SS, NN, BB, WW)                                                                                                            \
-    GG_LAUNCH(HIP_KERNEL_NAME(gg_split_kernel<KK, SS, NN, 2, BB, WW, (NN == 2)>), dim3(cdiv(cdiv(n_out, 32), BB / 64)), dim3(BB), 0, s, in, n_in, wps, \
-              nbr, n_out, k_vol, c_produce, bias, out, order, stats, cls_sorted, classes)
-        // one 32-channel chunk per stage, 256-thread workgroups; 32 produced channels: loads issued between the matrix groups (spconv_split.cuh has the numbers)
-        const int blk = 256;
-        const int kc = c_gather / 32, nt = c_produce / 16;
-        if (0) {}
-        else if (kc == 1 && nt == 2) SPL(1, 1, 2, 256, 4);
-        else if (kc == 1 && nt == 4) SPL(1, 1, 4, 256, 4);
-        else if (kc == 1 && nt == 8) SPL(1, 1, 8, 256, 3);
-        else if (kc == 2 && nt == 2) SPL(2, 1, 2, 256, 4);
-        else if (kc == 2 && nt == 4) SPL(2, 1, 4, 256, 4);
-        else if (kc == 2 && nt == 8) SPL(2, 1, 8, 256, 3);
-        else if (kc == 4 && nt == 2) SPL(4, 1, 2, 256, 4);
-        else if (kc == 4 && nt == 4) SPL(4, 1, 4, 256, 4);
-        else SPL(4, 1, 8, 256, 3);
-#undef SPL
-        TODA_LAUNCH_CHECK();
-        if (stats) {
-            fold_or_defer(stats, cdiv(cdiv(n_out, 32), blk / 64), c_produce, s);
-            TODA_LAUNCH_CHECK();
-        }
-        return TODA_OK;
-    }
-    // 128 -> 128: one 64 KiB slice shared by a 512-thread workgroup, 16 rows per wave (0.67 ms against 0.76 for two row tiles per
-    // wave and 0.70 for register-only weights on 97.5k x 27 x 128 x 128)
-    if (vec_ok && Q == 8 && NT == 8 && !cls_sorted) {
-        GG_LAUNCH(HIP_KERNEL_NAME(gather_gemm_lds_kernel<8, 8, 1, true, false, 512>), dim3(cdiv(cdiv(n_out, 16), 8)), dim3(512), 0, s, in, n_in,
-                  c_gather, wp, nbr, n_out, k_vol, c_produce, bias, out, order, stats);
-        TODA_LAUNCH_CHECK();
-        return TODA_OK;
-    }
-    if ((env_lds || stats) && !cls_sorted && vec_ok && Q * NT <= 32) {  // weight slice <= 32 KiB per buffer
-#define GL(QQ, NN, RR)                                                                                                   \
-    GG_LAUNCH(HIP_KERNEL_NAME(gather_gemm_lds_kernel<QQ, NN, RR, true, true, SC_BLOCK, false, (QQ <= 4 && NN <= 4 && RR == 2)>), \
-              dim3(cdiv(cdiv(n_out, 16 * RR), SC_BLOCK / 64)), dim3(SC_BLOCK), 0, s, in, n_in, c_gather, wp, nbr, n_out, k_vol,  \
-              c_produce, bias, out, order, stats)
-#define GL_ROW(QQ)                 \
-    switch (NT) {                  \
-        case 1: GL(QQ, 1, 2); break; \
-        case 2: GL(QQ, 2, 2); break; \
-        case 4: GL(QQ, 4, 2); break; \
-        default: GL(QQ, 8, 1); break; \
-    }
-        switch (Q) {
-            case 1: GL_ROW(1); break;
-            case 2: GL_ROW(2); break;
-            case 4: GL_ROW(4); break;
-            default: GL_ROW(8); break;
-        }
-#undef GL_ROW
-#undef GL
-        TODA_LAUNCH_CHECK();
-        if (stats) {      // fold the per-workgroup partial sums of the launch above (same grid arithmetic as GL / GL_ROW)
-            const int rr = NT >= 8 ? 1 : 2;
-            fold_or_defer(stats, cdiv(cdiv(n_out, 16 * rr), SC_BLOCK / 64), c_produce, s);
-            TODA_LAUNCH_CHECK();
-        }
-        return TODA_OK;
-    }
-    TODA_CHECK_ARG(stats == nullptr, "gather_gemm: statistics requested on a launch shape without the fused epilogue");
-    // register-resident weights (gather_gemm_kernel): the narrow, the "more gathered than produced" and the class-sorted launches
-#define GGV(QQ, NN, RR, VV)                                                                                           \
-    if (cls_sorted && (VV))                                                                                           \
-        GG_LAUNCH(HIP_KERNEL_NAME(gather_gemm_kernel<QQ, NN, RR, false, true, true>),                                 \
-                  dim3(cdiv(cdiv(n_out, 16 * RR), SC_BLOCK / 64)), dim3(SC_BLOCK), 0, s, in, n_in, c_gather, wp, nbr, \
-                  n_out, k_vol, c_produce, bias, out, 0, order, cls_sorted, classes);                                 \
-    else                                                                                                              \
-        GG_LAUNCH(HIP_KERNEL_NAME(gather_gemm_kernel<QQ, NN, RR, false, VV>),                                         \
-                  dim3(cdiv(cdiv(n_out, 16 * RR), SC_BLOCK / 64)), dim3(SC_BLOCK), 0, s, in, n_in, c_gather, wp, nbr, \
-                  n_out, k_vol, c_produce, bias, out, 0, order, nullptr, classes)
-#define GG_ROW(QQ)                                                                      \
-    switch (NT) {                                                                       \
-        case 1: GGV(QQ, 1, 2, true); break;                                             \
-        case 2: GGV(QQ, 2, 2, true); break;                                             \
-        case 4: GGV(QQ, 4, 2, true); break;                                             \
-        default:                                                                        \
-            if (QQ < 8) { GGV(QQ, 8, 1, true); } else { GGV(QQ, 8, 2, true); }           \
-            break;      /* 128 -> 128: two row tiles measured 16 % faster than one */    \
-    }
-    if (!vec_ok) {  // rows not 16-byte aligned (e.g. 5 point features): dword gathers
-        TODA_CHECK_ARG(Q == 1, "gather_gemm: gathered channel counts above 16 must be multiples of 4 (got %d)", c_gather);
-        switch (NT) {
-            case 1: GGV(1, 1, 2, false); break;
-            case 2: GGV(1, 2, 2, false); break;
-            case 4: GGV(1, 4, 2, false); break;
-            default: GGV(1, 8, 1, false); break;
-        }
-        TODA_LAUNCH_CHECK();
-        return TODA_OK;
-    }
-    switch (Q) {
-        case 1: GG_ROW(1); break;
-        case 2: GG_ROW(2); break;
-        case 4: GG_ROW(4); break;
-        default: GG_ROW(8); break;
-    }
-#undef GG_ROW
-#undef GGV
-    TODA_LAUNCH_CHECK();
-    return TODA_OK;
 }
 
 extern "C" int toda_spconv_gather_gemm(const float* in, int n_in, int c_gather, const float* wp, const int32_t* nbr,
@@ -1766,8 +1643,6 @@ extern "C" int toda_spconv_gather_gemm_compact_stats(const float* in, int n_in, 
     return TODA_OK;
 }
 
-// SubM gather-GEMM over a halo plan (toda_halo_plan_build): forward, and - with the transposed / offset-reversed packed operand - the
-// data gradient of the same table.  sums (nullable): BatchNorm moments from the epilogue, as toda_spconv_gather_gemm_stats.
 extern "C" size_t toda_spconv_wgrad_workspace_bytes(int n_out, int k_vol, int cin, int cout) {
     int chunks, rpc;
     wgrad_plan(n_out, k_vol, cin, cout, &chunks, &rpc);
@@ -1795,68 +1670,56 @@ extern "C" int toda_spconv_wgrad(const float* in, int n_in, const float* dout, c
     }
     const int MT = tiles_pow2(cin), NT = tiles_pow2(cout);
     static const int env_sub = getenv("TODA_WG_SUB") ? atoi(getenv("TODA_WG_SUB")) : 7;  // 128-channel sides take 8 tiles per block: 1.08 -> 0.76 ms on 97.5k x 27 x 128 x 128
-    int mtb = MT < 4 ? MT : 4, ntb = NT < 4 ? NT : 4;
-    if (MT == 8 && (env_sub & 1)) mtb = 8;
-    if (NT == 8 && (env_sub & 2)) ntb = 8;
-    const int nsub_m = MT / mtb, nsub_n = NT / ntb;
-    float* slab = (float*)ws;
     static const int env_wg_xcd = getenv("TODA_WG_XCD") ? atoi(getenv("TODA_WG_XCD")) : 1;
     const int chunks_launch = env_wg_xcd ? (chunks + 7) / 8 * 8 : chunks;      // padded to whole rounds of the 8 XCDs: blocks of the padding chunks leave at once
     const int xcd_chunks = env_wg_xcd ? chunks_launch : -chunks;
-    if (matrix_path() == 1 && toda::wgrad_split_shape_ok(cin, cout)) {      // matrix path "split": spconv_split.cuh
-        const dim3 g(chunks_launch * k_vol);
-#define WGS(MM, NN)                                                                                                                       \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad_split_kernel<MM, NN>), g, dim3(SC_BLOCK), 0, s, in, n_in, dout, nbr, n_out, k_vol, rpc, slab, \
-                       xcd_chunks)
-        if (cin == 128 && cout == 128) hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad_split_kernel<4, 4, 2, 2>), g, dim3(SC_BLOCK), 0, s, in, n_in, dout, nbr, n_out, k_vol, rpc, slab, xcd_chunks);
-        else if (cin == 64 && cout == 128) hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad_split_kernel<4, 4, 1, 2>), g, dim3(SC_BLOCK), 0, s, in, n_in, dout, nbr, n_out, k_vol, rpc, slab, xcd_chunks);
-        else if (cin == 128 && cout == 64) hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad_split_kernel<4, 4, 2, 1>), g, dim3(SC_BLOCK), 0, s, in, n_in, dout, nbr, n_out, k_vol, rpc, slab, xcd_chunks);
-        else if (cin == 32 && cout == 32) WGS(2, 2);
-        else if (cin == 32) WGS(2, 4);
-        else if (cout == 32) WGS(4, 2);
-        else WGS(4, 4);
-#undef WGS
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(elems, SC_BLOCK)), dim3(SC_BLOCK), 0, s, slab, chunks, elems, dw);
-        TODA_LAUNCH_CHECK();
-        return TODA_OK;
-    }
-    if (MT == 8 && NT == 8 && (env_sub & 4)) {   // cooperative quarters: 0.75 -> 0.68 ms on 97.5k x 27 x 128 x 128
-        if (cin == 128 && cout == 128)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad_kernel<4, 4, true, true>), dim3(chunks_launch * k_vol), dim3(SC_BLOCK), 0, s, in, n_in, cin, dout,
-                               cout, nbr, n_out, k_vol, rpc, MT, NT, 2, slab, xcd_chunks);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad_kernel<4, 4, true>), dim3(chunks_launch * k_vol), dim3(SC_BLOCK), 0, s, in, n_in, cin, dout,
-                               cout, nbr, n_out, k_vol, rpc, MT, NT, 2, slab, xcd_chunks);
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(elems, SC_BLOCK)), dim3(SC_BLOCK), 0, s, slab, chunks, elems, dw);
-        TODA_LAUNCH_CHECK();
-        return TODA_OK;
-    }
-    const dim3 grid(chunks_launch * k_vol * nsub_m * nsub_n);
     const bool exact = cin == 16 * MT && cout == 16 * NT;
-#define WG(MM, NN)                                                                                                  \
-    if (exact)                                                                                                      \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad_kernel<MM, NN, false, true>), grid, dim3(SC_BLOCK), 0, s, in, n_in, cin, dout, cout, nbr, \
-                           n_out, k_vol, rpc, MT, NT, nsub_n, slab, xcd_chunks);                                    \
-    else                                                                                                            \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(wgrad_kernel<MM, NN>), grid, dim3(SC_BLOCK), 0, s, in, n_in, cin, dout, cout, nbr, \
-                       n_out, k_vol, rpc, MT, NT, nsub_n, slab, xcd_chunks)
-#define WG_ROW(MM)             \
-    switch (ntb) {             \
-        case 1: WG(MM, 1); break; \
-        case 2: WG(MM, 2); break; \
-        case 4: WG(MM, 4); break; \
-        default: WG(MM, 8); break; \
+    float* slab = (float*)ws;
+
+    // the route: kernel family, tiles per block of each side, channel sub-blocks along cout, workgroups
+    enum { SPLIT, COOP, TILED } family;
+    int mtb = MT < 4 ? MT : 4, ntb = NT < 4 ? NT : 4, nsub_n = 1, grid = chunks_launch * k_vol;
+    if (matrix_path() == 1 && toda::wgrad_split_shape_ok(cin, cout)) {      // matrix path "split": spconv_split.cuh
+        family = SPLIT;
+    } else if (MT == 8 && NT == 8 && (env_sub & 4)) {   // cooperative quarters: 0.75 -> 0.68 ms on 97.5k x 27 x 128 x 128
+        family = COOP, nsub_n = 2;
+    } else {
+        family = TILED;
+        if (MT == 8 && (env_sub & 1)) mtb = 8;
+        if (NT == 8 && (env_sub & 2)) ntb = 8;
+        nsub_n = NT / ntb;
+        grid *= (MT / mtb) * nsub_n;
     }
-    switch (mtb) {
-        case 1: WG_ROW(1); break;
-        case 2: WG_ROW(2); break;
-        case 4: WG_ROW(4); break;
-        default: WG_ROW(8); break;
+    auto split = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(SC_BLOCK), 0, s, in, n_in, dout, nbr, n_out, k_vol, rpc, slab, xcd_chunks);
+    };
+    auto native = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(SC_BLOCK), 0, s, in, n_in, cin, dout, cout, nbr, n_out, k_vol, rpc, MT, NT, nsub_n, slab,
+                           xcd_chunks);
+    };
+    switch (family) {
+        case SPLIT:      // 32 / 64 channels a side: one block; 128: two 64-channel quarters along that side
+            if (cin == 128 && cout == 128) split(wgrad_split_kernel<4, 4, 2, 2>);
+            else if (cin == 64 && cout == 128) split(wgrad_split_kernel<4, 4, 1, 2>);
+            else if (cin == 128 && cout == 64) split(wgrad_split_kernel<4, 4, 2, 1>);
+            else if (cin == 32 && cout == 32) split(wgrad_split_kernel<2, 2>);
+            else if (cin == 32) split(wgrad_split_kernel<2, 4>);
+            else if (cout == 32) split(wgrad_split_kernel<4, 2>);
+            else split(wgrad_split_kernel<4, 4>);
+            break;
+        case COOP:
+            if (exact) native(wgrad_kernel<4, 4, true, true>);
+            else native(wgrad_kernel<4, 4, true>);
+            break;
+        case TILED:
+            with_tiles(mtb, ntb, [&](auto m, auto n) {
+                constexpr int MTB = decltype(m)::value, NTB = decltype(n)::value;
+                if (exact) native(wgrad_kernel<MTB, NTB, false, true>);
+                else native(wgrad_kernel<MTB, NTB>);
+            });
+            break;
     }
-#undef WG_ROW
-#undef WG
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(elems, SC_BLOCK)), dim3(SC_BLOCK), 0, s, slab, chunks, elems, dw);
     TODA_LAUNCH_CHECK();
     return TODA_OK;
 }
-

@@ -118,29 +118,29 @@ split_pack_batch_kernel(const SplitPackBatch b) {
 }
 
 // ---- the kernel -------------------------------------------------------------------------------------------------------------------
-// A STAGE is KCS of the KC 32-channel chunks of one offset: its weight slice (KCS NT 3 KiB) is what the workgroup shares through LDS
-// (double buffered, LDS-DMA), its rows' 128 KCS bytes per row are what a lane gathers one stage ahead.  64 -> 64: one stage per offset
-// (24 KiB); 128 -> 128: four stages per offset (24 KiB each: the whole 96 KiB slice of an offset would not fit twice).
-// BLK threads = BLK / 64 waves share the slice: every workgroup re-reads the whole packed operand, so with 256-thread workgroups the
-// slices are HALF of the kernel's vector-memory traffic at 64 -> 64 (2.0 GB beside 1.9 GB of gathered rows at 389 k rows).
-// Measured (C3 / C5 levels, ms per launch): ONE chunk per stage wins wherever it was tried - 64 -> 64 @ 389 k rows 0.346 (256 threads,
-// KCS 1: 122 registers, 4 waves per SIMD, 24 KiB of LDS) against 0.354 (768 threads, KCS 2) and 0.367 (256, KCS 2: 168 registers, 3 waves);
-// @ 117 k rows 0.124 / 0.179 / 0.135; strided 64 -> 64 forward 0.104 / 0.154 / 0.122: more resident waves hide more of the gathers.
-template <int KC, int KCS, int NT, int RT, int BLK, int WAVES, bool IL = false>
-__global__ void __launch_bounds__(BLK, WAVES)
+// A STAGE is ONE of the KC 32-channel chunks of one offset: its weight slice (NT 3 KiB) is what the workgroup shares through LDS
+// (double buffered, LDS-DMA), its rows' 128 bytes per row are what a lane gathers one stage ahead.  32 -> 64: one stage per offset
+// (12 KiB); 128 -> 128: four stages per offset (24 KiB each: the whole 96 KiB slice of an offset would not fit twice).
+// The 4 waves of a 256-thread workgroup share the slice and own two 16-row tiles each: every workgroup re-reads the whole packed operand, so
+// the slices are HALF of the kernel's vector-memory traffic at 64 -> 64 (2.0 GB beside 1.9 GB of gathered rows at 389 k rows).
+// Measured (C3 / C5 levels, ms per launch) when chunks per stage and threads per workgroup were still parameters: ONE chunk per stage won
+// wherever it was tried - 64 -> 64 @ 389 k rows 0.346 (256 threads, one chunk: 122 registers, 4 waves per SIMD, 24 KiB of LDS) against 0.354
+// (768 threads, two chunks) and 0.367 (256, two chunks: 168 registers, 3 waves); @ 117 k rows 0.124 / 0.179 / 0.135; strided 64 -> 64 forward
+// 0.104 / 0.154 / 0.122: more resident waves hide more of the gathers.
+template <int KC, int NT, int WAVES, bool IL = false>
+__global__ void __launch_bounds__(SC_BLOCK, WAVES)
 gg_split_kernel(const float* __restrict__ in, int n_in, const u32x4* __restrict__ wps, const int* __restrict__ nbr, int n_out, int K, int cp,
                 const float* __restrict__ bias, float* __restrict__ out, const int* __restrict__ order, double* __restrict__ stats,
                 const unsigned char* __restrict__ cls_sorted, const GatherClasses classes) {
-    static_assert(KC % KCS == 0, "whole stages per offset");
+    constexpr int RT = 2;                    // 16-row tiles per wave
     constexpr int CG = 32 * KC;
-    constexpr int SPO = KC / KCS;            // stages per offset
-    constexpr int UNITS = KCS * NT * 3;      // 1 KiB wave-instruction images per stage
+    constexpr int UNITS = NT * 3;            // 1 KiB wave-instruction images per stage
     constexpr int SLICE = UNITS * 64;        // u32x4 per stage
-    static_assert(2 * SLICE * 16 >= (BLK / 64) * 2 * 16 * NT * 4, "the statistics scratch aliases the weight buffers");
+    static_assert(2 * SLICE * 16 >= (SC_BLOCK / 64) * 2 * 16 * NT * 4, "the statistics scratch aliases the weight buffers");
     __shared__ u32x4 wl[2 * SLICE];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int blk = xcd_chunked_block(blockIdx.x, gridDim.x);
-    const int wave = blk * (BLK / 64) + wv;
+    const int wave = blk * (SC_BLOCK / 64) + wv;
     const int r = lane & 15, g = lane >> 4;
     const int row0 = wave * (16 * RT);
 
@@ -175,7 +175,7 @@ gg_split_kernel(const float* __restrict__ in, int n_in, const u32x4* __restrict_
         __syncthreads();
         int cb = cw[0];
 #pragma unroll
-        for (int w = 1; w < BLK / 64; ++w) cb = (cw[w] == cb) ? cb : -1;
+        for (int w = 1; w < SC_BLOCK / 64; ++w) cb = (cw[w] == cb) ? cb : -1;
         __syncthreads();                          // before the first slice lands in wl
         if (cb >= 0 && classes.count[cb & 7] > 0 && classes.count[cb & 7] <= 8) {
             listed = true;
@@ -193,31 +193,31 @@ gg_split_kernel(const float* __restrict__ in, int n_in, const u32x4* __restrict_
             dst[rt] = __builtin_nontemporal_load(nbr + (size_t)kk * n_out + rows[rt]);      // past the last offset: its ids again, never used
         }
     };
-    // rows of stage `part` of an offset: the lane's 16 bytes of the 64-byte segments 2 KCS part .. 2 KCS (part + 1) - 1
-    auto gather = [&](const int (&src)[RT], int part, bool valid, f32x4 (&raw)[RT][2 * KCS]) {      // valid (wave-uniform): the offset exists
+    // rows of stage `part` of an offset: the lane's 16 bytes of the 64-byte segments 2 part and 2 part + 1
+    auto gather = [&](const int (&src)[RT], int part, bool valid, f32x4 (&raw)[RT][2]) {      // valid (wave-uniform): the offset exists
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) {
             const bool ok = src[rt] >= 0 && valid;
-            const unsigned base = (unsigned)src[rt] * (unsigned)(CG * 4) + (unsigned)(16 * g) + (unsigned)(128 * KCS) * (unsigned)part;
+            const unsigned base = (unsigned)src[rt] * (unsigned)(CG * 4) + (unsigned)(16 * g) + 128u * (unsigned)part;
 #pragma unroll
-            for (int i = 0; i < 2 * KCS; ++i)
+            for (int i = 0; i < 2; ++i)
                 raw[rt][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, ok ? base + 64u * i : OOB, 0, 0));
         }
     };
-    auto gather_rt = [&](const int (&src)[RT], int part, bool valid, f32x4 (&raw)[RT][2 * KCS], int rt) {
+    auto gather_rt = [&](const int (&src)[RT], int part, bool valid, f32x4 (&raw)[RT][2], int rt) {
         const bool ok = src[rt] >= 0 && valid;
-        const unsigned base = (unsigned)src[rt] * (unsigned)(CG * 4) + (unsigned)(16 * g) + (unsigned)(128 * KCS) * (unsigned)part;
+        const unsigned base = (unsigned)src[rt] * (unsigned)(CG * 4) + (unsigned)(16 * g) + 128u * (unsigned)part;
 #pragma unroll
-        for (int i = 0; i < 2 * KCS; ++i)
+        for (int i = 0; i < 2; ++i)
             raw[rt][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, ok ? base + 64u * i : OOB, 0, 0));
     };
-    auto stage = [&](int st, int buf) {       // the slice of stage st = j SPO + part: global -> LDS, 1 KiB per wave-instruction, no registers
-        const int sc = st < KE * SPO ? st : KE * SPO - 1;
-        const int ss = kof(sc / SPO) * SPO + sc % SPO;
+    auto stage = [&](int st, int buf) {       // the slice of stage st = j KC + part: global -> LDS, 1 KiB per wave-instruction, no registers
+        const int sc = st < KE * KC ? st : KE * KC - 1;
+        const int ss = kof(sc / KC) * KC + sc % KC;
 #pragma unroll
-        for (int t = 0; t < (UNITS + BLK / 64 - 1) / (BLK / 64); ++t) {
-            const int u = t * (BLK / 64) + wv;
-            if (UNITS % (BLK / 64) == 0 || u < UNITS)
+        for (int t = 0; t < (UNITS + SC_BLOCK / 64 - 1) / (SC_BLOCK / 64); ++t) {
+            const int u = t * (SC_BLOCK / 64) + wv;
+            if (UNITS % (SC_BLOCK / 64) == 0 || u < UNITS)
                 __builtin_amdgcn_global_load_lds(reinterpret_cast<const float*>(wps + (size_t)ss * SLICE + u * 64 + lane),
                                                  reinterpret_cast<float*>(&wl[buf * SLICE + u * 64]), 16, 0, 0);
         }
@@ -226,7 +226,7 @@ gg_split_kernel(const float* __restrict__ in, int n_in, const u32x4* __restrict_
     // ids live in three register sets that rotate by NAME (the loop body is written three times): a copy of a set whose load is
     // still in flight, or the "row exists" select applied at load time, would be a wait for that load at the end of every offset
     int idA[RT], idB[RT], idC[RT];
-    f32x4 raw[RT][2 * KCS];
+    f32x4 raw[RT][2];
     load_ids(0, idA);
     load_ids(1, idB);
     stage(0, 0);
@@ -243,18 +243,16 @@ gg_split_kernel(const float* __restrict__ in, int n_in, const u32x4* __restrict_
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) any = any || __any(ids_cur[rt] >= 0);
 #pragma unroll
-        for (int part = 0; part < SPO; ++part) {
-            const int cur = (k * SPO + part) & 1;
+        for (int part = 0; part < KC; ++part) {
+            const int cur = (k * KC + part) & 1;
             // one straight-line body per (wave, offset) that has a neighbour in any of its rows: on the submanifold tables 0.83 of the
             // executed tile rows are pairs this way against 0.85 with a test per 16-row tile (C3, 389 k rows) - not worth three bodies
             // (hipcc joins them with 32 accumulator copies per offset)
-            u32x4 ah[RT][KCS], am[RT][KCS], al[RT][KCS];
-            f32x4 (&rw)[RT][2 * KCS] = raw;      // this stage's rows
+            u32x4 ah[RT], am[RT], al[RT];
+            f32x4 (&rw)[RT][2] = raw;      // this stage's rows
             if (any) {
 #pragma unroll
-                for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-                    for (int kc = 0; kc < KCS; ++kc) sp_split8(rw[rt][2 * kc], rw[rt][2 * kc + 1], ah[rt][kc], am[rt][kc], al[rt][kc]);
+                for (int rt = 0; rt < RT; ++rt) sp_split8(rw[rt][0], rw[rt][1], ah[rt], am[rt], al[rt]);
             }
             SP_STAMP(0);
             if constexpr (IL) {
@@ -267,31 +265,30 @@ gg_split_kernel(const float* __restrict__ in, int n_in, const u32x4* __restrict_
                 // 64 -> 64 (SP_ABLATE): without matrix instructions 0.232 ms, without row gathers 0.245, without slice DMA 0.307, without the
                 // operand split 0.361 of 0.365 - the L2 -> CU path alone needs two thirds of the kernel's time (4 GB per launch: 1.9 GB of
                 // 64-byte row segments + 2.0 GB of weight slices), the vector pipe is hidden, and what is left is imperfect overlap.
-                constexpr int ITER = KCS * NT, PIECES = RT + 2;      // slice | rows of tile 0 .. RT-1 | ids
+                constexpr int PIECES = RT + 2;      // slice | rows of tile 0 .. RT-1 | ids
                 auto piece = [&](int p) {
                     if (p == 0) {
 #if !(SP_ABLATE & 4)
-                        stage(k * SPO + part + 1, cur ^ 1);
+                        stage(k * KC + part + 1, cur ^ 1);
 #endif
                     } else if (p <= RT) {
-                        if (part + 1 < SPO) gather_rt(ids_cur, part + 1, true, raw, p - 1);
+                        if (part + 1 < KC) gather_rt(ids_cur, part + 1, true, raw, p - 1);
                         else gather_rt(ids_nxt, 0, k + 1 < KE, raw, p - 1);
-                    } else if (part == SPO - 1) load_ids(k + 2, ids_new);
+                    } else if (part == KC - 1) load_ids(k + 2, ids_new);
                     asm volatile("" ::: "memory");
                 };
                 if (any) {
                     const u32x4* __restrict__ wb = wl + cur * SLICE + lane;
 #pragma unroll
-                    for (int st = 0; st < ITER; ++st) {
-                        const int kc = st / NT, n = st % NT;
-                        const bf16x8 bh = __builtin_bit_cast(bf16x8, wb[(st * 3 + 0) * 64]), bm = __builtin_bit_cast(bf16x8, wb[(st * 3 + 1) * 64]),
-                                     bl = __builtin_bit_cast(bf16x8, wb[(st * 3 + 2) * 64]);
+                    for (int n = 0; n < NT; ++n) {
+                        const bf16x8 bh = __builtin_bit_cast(bf16x8, wb[(n * 3 + 0) * 64]), bm = __builtin_bit_cast(bf16x8, wb[(n * 3 + 1) * 64]),
+                                     bl = __builtin_bit_cast(bf16x8, wb[(n * 3 + 2) * 64]);
 #pragma unroll
                         for (int p = 0; p < PIECES; ++p)
-                            if (p * ITER / PIECES == st) piece(p);
+                            if (p * NT / PIECES == n) piece(p);
 #define SP_TERM(AA, BB)                                                                                                              \
     _Pragma("unroll") for (int rt = 0; rt < RT; ++rt)                                                                                \
-        acc[rt][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, AA[rt][kc]), BB, acc[rt][n], 0, 0, 0)
+        acc[rt][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, AA[rt]), BB, acc[rt][n], 0, 0, 0)
                         SP_TERM(al, bh);
                         SP_TERM(ah, bl);
                         SP_TERM(am, bm);
@@ -308,17 +305,17 @@ gg_split_kernel(const float* __restrict__ in, int n_in, const u32x4* __restrict_
             // issue order = the order the waits below and at the top of the next stage retire them in: the slice of the next stage (needed
             // by every wave behind the barrier), the rows of the next stage, the ids of offset k + 2
 #if !(SP_ABLATE & 4)
-            stage(k * SPO + part + 1, cur ^ 1);
+            stage(k * KC + part + 1, cur ^ 1);
 #endif
             asm volatile("" ::: "memory");
 #if SP_ABLATE & 8
             if (k < 0)
 #endif
-            if (part + 1 < SPO) gather(ids_cur, part + 1, true, raw);
+            if (part + 1 < KC) gather(ids_cur, part + 1, true, raw);
             else gather(ids_nxt, 0, k + 1 < KE, raw);          // in flight under the matrix work below
             asm volatile("" ::: "memory");
 #if !(SP_ABLATE & 16)
-            if (part == SPO - 1) load_ids(k + 2, ids_new);
+            if (part == KC - 1) load_ids(k + 2, ids_new);
 #endif
             asm volatile("" ::: "memory");
             SP_STAMP(1);
@@ -327,18 +324,17 @@ gg_split_kernel(const float* __restrict__ in, int n_in, const u32x4* __restrict_
                 // (reading the three planes of a step one step ahead of its matrix instructions - 12 more registers, the order pinned
                 // with sched_group_barrier - measured nothing at three waves per SIMD and spilled in the widest variants)
 #pragma unroll
-                for (int st = 0; st < KCS * NT; ++st) {
-                    const int kc = st / NT, n = st % NT;
-                    const bf16x8 bh = __builtin_bit_cast(bf16x8, wb[(st * 3 + 0) * 64]), bm = __builtin_bit_cast(bf16x8, wb[(st * 3 + 1) * 64]),
-                                 bl = __builtin_bit_cast(bf16x8, wb[(st * 3 + 2) * 64]);
+                for (int n = 0; n < NT; ++n) {
+                    const bf16x8 bh = __builtin_bit_cast(bf16x8, wb[(n * 3 + 0) * 64]), bm = __builtin_bit_cast(bf16x8, wb[(n * 3 + 1) * 64]),
+                                 bl = __builtin_bit_cast(bf16x8, wb[(n * 3 + 2) * 64]);
 #if SP_ABLATE & 2
 #define SP_TERM(AA, BB)                                                                                                              \
     _Pragma("unroll") for (int rt = 0; rt < RT; ++rt)                                                                                \
-        acc[rt][n][0] += __builtin_bit_cast(float, AA[rt][kc][0] ^ __builtin_bit_cast(u32x4, BB)[0])
+        acc[rt][n][0] += __builtin_bit_cast(float, AA[rt][0] ^ __builtin_bit_cast(u32x4, BB)[0])
 #else
 #define SP_TERM(AA, BB)                                                                                                              \
     _Pragma("unroll") for (int rt = 0; rt < RT; ++rt)                                                                                \
-        acc[rt][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, AA[rt][kc]), BB, acc[rt][n], 0, 0, 0)
+        acc[rt][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, AA[rt]), BB, acc[rt][n], 0, 0, 0)
 #endif
                     SP_TERM(al, bh);
                     SP_TERM(ah, bl);
@@ -356,8 +352,8 @@ gg_split_kernel(const float* __restrict__ in, int n_in, const u32x4* __restrict_
 #if SP_ABLATE & (4 | 8 | 16)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #else
-            if (part == SPO - 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(RT * 2 * KCS + RT) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(RT * 2 * KCS) : "memory");
+            if (part == KC - 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(RT * 2 + RT) : "memory");
+            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(RT * 2) : "memory");
 #endif
             SP_STAMP(3);
             __builtin_amdgcn_s_barrier();
@@ -412,7 +408,7 @@ gg_split_kernel(const float* __restrict__ in, int n_in, const u32x4* __restrict_
             const int qq = threadIdx.x / cp, ch = threadIdx.x - qq * cp;
             double a = 0.0;
 #pragma unroll
-            for (int w = 0; w < BLK / 64; ++w) a += (double)st_sh[w][qq][ch];
+            for (int w = 0; w < SC_BLOCK / 64; ++w) a += (double)st_sh[w][qq][ch];
             stats[2 * cp + (size_t)(qq * cp + ch) * gridDim.x + blk] = a;
         }
     }
