@@ -631,17 +631,28 @@ int toda_spconv_gather_gemm_stats_partials(const float* in, int n_in, int c_gath
  *   toda_conv3x3_transform_weight u = G w G^T in the kernel's operand order; mode 0: forward,
  *                                 mode 1: data gradient (filters rotated by 180 degrees, channel roles swapped),
  *                                 mode 2: both, forward operand first (2 x toda_conv3x3_weight_floats floats)
+ *   toda_conv3x3_transform_weight_batch  the same for n layers in one launch (16 layers per launch): table is a HOST
+ *                                 array of {w, cout, cin, mode, u} entries; every u[i] gets the bits the per-layer call
+ *                                 writes.  Once per step for the stride-1 3x3 layers of a dense stack.
  *   toda_conv3x3_fwd              y[B][cout][H][W] = conv(x[B][cin][H][W]) (+ bias[cout], nullable).  With the
  *                                 mode-1 operand and (cin, cout) = (Cout, Cin) of the layer it computes dX from dY.
  *                                 ws: toda_conv3x3_workspace_bytes() bytes, ZERO before the first call and used by
  *                                 one call at a time (hand-off flags, which every call leaves zero again, +
  *                                 partial-sum slabs of the stream-K work split)
  *   toda_conv3x3_wgrad            dw[Cout][Cin][3][3] from x and dy (workspace: per-split partial sums, folded
- *                                 in fixed order - deterministic, no float atomics)
+ *                                 in fixed order - deterministic, no float atomics).  The fold and G^T . G are one
+ *                                 kernel; TODA_WGRAD_FOLD=pair runs them as two with the per-unit sums in the
+ *                                 workspace between them (same bits).
  * ---------------------------------------------------------------------- */
 int toda_conv3x3_supported(int batch, int cin, int cout, int H, int W);
 size_t toda_conv3x3_weight_floats(int cout, int cin);
 int toda_conv3x3_transform_weight(const float* w, int cout, int cin, int mode, float* u, void* stream);
+typedef struct toda_conv3x3_weight_entry {
+    const float* w; /* [cout][cin][3][3] */
+    int32_t cout, cin, mode, reserved;
+    float* u;       /* toda_conv3x3_weight_floats(cout, cin) floats, twice that for mode 2 */
+} toda_conv3x3_weight_entry;
+int toda_conv3x3_transform_weight_batch(const toda_conv3x3_weight_entry* table_host, int n, void* stream);
 size_t toda_conv3x3_workspace_bytes(void);
 size_t toda_conv3x3_wgrad_workspace_bytes(int batch, int cin, int cout, int H, int W);
 int toda_conv3x3_wgrad(const float* x, const float* dy, int batch, int cin, int cout, int H, int W, float* dw,

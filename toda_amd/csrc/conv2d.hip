@@ -26,6 +26,7 @@
 // pcdet/models/dense_heads/center_head.py:20-28,73-80 (reference paths).
 #include <hip/hip_ext.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include "common.h"
 
@@ -105,13 +106,11 @@ __device__ __forceinline__ void wn_a(float y0, float y1, float y2, float y3, flo
 // mode 0: g = w[cout][cin] (forward);  mode 1: g = rot180(w[cin][cout]) with the channel roles swapped (dgrad).
 // w is torch's [Cout][Cin][3][3].  CO / CI below are the channel counts of the convolution that will RUN.
 // ------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(WN_BLOCK)
-wino_weight_kernel(const float* __restrict__ w, int cout, int cin, int mode, float* __restrict__ u) {
+__device__ __forceinline__ void wn_weight_element(const float* __restrict__ w, int cout, int cin, int mode, float* __restrict__ u, unsigned e) {
     // one thread per (cb, chunk, frequency row fi, position in the 256-float image row): the six frequencies (fi, 0..5) are
     // six stores with the whole wave on consecutive floats; mode 2 writes the forward operand followed by the data-gradient
     // operand (36 * cout * cin floats each)
     const unsigned per = (unsigned)6 * cout * cin;          // threads per operand
-    unsigned e = blockIdx.x * WN_BLOCK + threadIdx.x;
     if (e >= (mode == 2 ? 2 * per : per)) return;
     const int md = mode == 2 ? (e >= per ? 1 : 0) : mode;
     float* dst = u;
@@ -140,6 +139,30 @@ wino_weight_kernel(const float* __restrict__ w, int cout, int cin, int mode, flo
     dst += ((size_t)(cb * n_chunks + chunk) * WN_FREQ + fi * 6) * WN_IMG + (e & 255u);
 #pragma unroll
     for (int fj = 0; fj < 6; ++fj) dst[(size_t)fj * WN_IMG] = (float)(tb[0] * WN_G[fj][0] + tb[1] * WN_G[fj][1] + tb[2] * WN_G[fj][2]);
+}
+
+__global__ void __launch_bounds__(WN_BLOCK)
+wino_weight_kernel(const float* __restrict__ w, int cout, int cin, int mode, float* __restrict__ u) {
+    wn_weight_element(w, cout, cin, mode, u, blockIdx.x * WN_BLOCK + threadIdx.x);
+}
+
+// The filter transforms of a whole stack of layers (and both operands of each) in ONE launch: a training step transforms every
+// layer's filters once, and a launch per layer is 13 kernels of 2-9 us alone on the GPU.  Layer l owns the blocks
+// [first_block[l], first_block[l + 1]); per element the arithmetic is wn_weight_element's, so the operands have the same bits.
+constexpr int WB_MAX_LAYERS = 16;
+struct WeightBatch {
+    const float* w[WB_MAX_LAYERS];
+    float* u[WB_MAX_LAYERS];
+    int cout[WB_MAX_LAYERS], cin[WB_MAX_LAYERS], mode[WB_MAX_LAYERS];
+    unsigned first_block[WB_MAX_LAYERS + 1];
+    int n;
+};
+
+__global__ void __launch_bounds__(WN_BLOCK)
+wino_weight_batch_kernel(const WeightBatch b) {
+    int l = 0;
+    while (l + 1 < b.n && blockIdx.x >= b.first_block[l + 1]) ++l;
+    wn_weight_element(b.w[l], b.cout[l], b.cin[l], b.mode[l], b.u[l], (blockIdx.x - b.first_block[l]) * WN_BLOCK + threadIdx.x);
 }
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t wn_rsrc(const float* base, unsigned bytes) {
@@ -1040,6 +1063,108 @@ wino_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ dy, con
     }
 }
 
+// The workgroups of the stream-K split whose range touched `unit`, in workgroup order: the slabs (w + unit) that hold its partial sums.
+__device__ __forceinline__ int wn_unit_segments(int unit, int n_units, int steps_per_unit, int G, int* __restrict__ seg) {
+    const long long S = (long long)n_units * steps_per_unit;
+    const long long u_lo = (long long)unit * steps_per_unit, u_hi = u_lo + steps_per_unit;
+    int w0 = (int)(u_lo * G / S);
+    while (w0 > 0 && ws_range_lo(w0, G, S) > u_lo) --w0;
+    while (w0 + 1 < G && ws_range_lo(w0 + 1, G, S) <= u_lo) ++w0;
+    int n = 0;
+    long long lo = ws_range_lo(w0, G, S);
+    for (int w = w0; w < G && lo < u_hi; ++w) {
+        const long long next = ws_range_lo(w + 1, G, S);
+        if (next > u_lo && next != lo) seg[n++] = w;
+        lo = next;
+    }
+    return n;
+}
+
+// dw[3][3] of one (co, ci) = G^T dU G in fp64 from its 36 folded sums
+__device__ __forceinline__ void wn_filter_grad(const double (&du)[WN_FREQ], float* __restrict__ out) {
+    double t[3][6];     // G^T dU: t[a][j] = sum_i G[i][a] dU[i][j]
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            double acc = 0.0;
+#pragma unroll
+            for (int i = 0; i < 6; ++i) acc += WN_G[i][a] * du[i * 6 + j];
+            t[a][j] = acc;
+        }
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+            double acc = 0.0;
+#pragma unroll
+            for (int j = 0; j < 6; ++j) acc += t[a][j] * WN_G[j][b];
+            out[a * 3 + b] = (float)acc;
+        }
+}
+
+// Fold and G^T . G in one kernel (the default): a workgroup owns one co row of a unit = 32 (co, ci) pairs, 128 consecutive bytes of
+// every frequency plane of a slab.  Its 256 threads split the 36 x 32 sums (4.5 each, the loads of eight segments of all of a
+// thread's sums in flight together, added in workgroup order as in wino_wgrad_reduce_kernel: the same bits), hand them over
+// through LDS, and the 32 pair threads apply G^T dU G.  32 workgroups per unit keep as many loads in flight over the slabs as the
+// one-thread-per-element fold did, and the per-unit sums never travel to HBM and back.
+constexpr int WF_PAIRS = 32;                                        // pairs per workgroup
+constexpr int WF_SUMS = (WN_FREQ * WF_PAIRS + WN_BLOCK - 1) / WN_BLOCK;   // sums per thread (the last one on half the threads)
+
+__global__ void __launch_bounds__(WN_BLOCK)
+wino_wgrad_fold_kernel(const float* __restrict__ slabs, const WgradGeom wg, int G, float* __restrict__ dw) {
+    __shared__ int seg[WS_MAX_GRID];
+    __shared__ int n_seg;
+    __shared__ float du_s[WN_FREQ * WF_PAIRS];
+    const int tid = threadIdx.x;
+    const int unit = blockIdx.x >> 5, row = blockIdx.x & 31;        // 1024 / WF_PAIRS = 32 workgroups per unit
+    if (tid == 0) n_seg = wn_unit_segments(unit, wg.n_units, wg.steps_per_unit, G, seg);
+    __syncthreads();
+    const int n = n_seg;
+    // sum k of this thread: element (f, p) = idx / 32, idx % 32 of the workgroup's [36][32] block; a thread without a last sum
+    // folds its first one again and drops it
+    const float* p[WF_SUMS];
+    float acc[WF_SUMS];
+#pragma unroll
+    for (int k = 0; k < WF_SUMS; ++k) {
+        const int idx = tid + k * WN_BLOCK < WN_FREQ * WF_PAIRS ? tid + k * WN_BLOCK : tid;
+        p[k] = slabs + (size_t)unit * WG_SLAB_FLOATS + (idx >> 5) * 1024 + row * 32 + (idx & 31);
+        acc[k] = 0.0f;
+    }
+    int i = 0;
+    for (; i + 8 <= n; i += 8) {
+        float v[WF_SUMS][8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const size_t off = (size_t)seg[i + j] * WG_SLAB_FLOATS;
+#pragma unroll
+            for (int k = 0; k < WF_SUMS; ++k) v[k][j] = p[k][off];
+        }
+#pragma unroll
+        for (int k = 0; k < WF_SUMS; ++k)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc[k] += v[k][j];
+    }
+    for (; i < n; ++i) {
+        const size_t off = (size_t)seg[i] * WG_SLAB_FLOATS;
+#pragma unroll
+        for (int k = 0; k < WF_SUMS; ++k) acc[k] += p[k][off];
+    }
+#pragma unroll
+    for (int k = 0; k < WF_SUMS; ++k)
+        if (tid + k * WN_BLOCK < WN_FREQ * WF_PAIRS) du_s[tid + k * WN_BLOCK] = acc[k];
+    __syncthreads();
+    if (tid >= WF_PAIRS) return;
+    double du[WN_FREQ];
+#pragma unroll
+    for (int f = 0; f < WN_FREQ; ++f) du[f] = (double)du_s[f * WF_PAIRS + tid];
+    const int cib = unit / wg.n_co_blocks, cob = unit - cib * wg.n_co_blocks;
+    const int co = cob * 32 + row, ci = cib * 32 + tid;
+    wn_filter_grad(du, dw + ((size_t)co * wg.g.Cin + ci) * 9);
+}
+
+// The same in two kernels with the per-unit sums in HBM between them (TODA_WGRAD_FOLD=pair: the A/B knob and the reference the
+// fused fold is tested against).
 // stage 1 of the fold: red[unit][f][co][ci] = sum of the unit's segment slabs in workgroup order (one thread per element:
 // coalesced, and enough threads even when a 64-channel layer has 4 units cut into 64 segments each)
 template <int SLAB>
@@ -1053,21 +1178,7 @@ wino_wgrad_reduce_kernel(const float* __restrict__ slabs, const int n_units, con
     __shared__ int n_seg;
     const long long e = (long long)blockIdx.x * WN_BLOCK + threadIdx.x;
     const int unit = (int)(((long long)blockIdx.x * WN_BLOCK) / SLAB);
-    if (threadIdx.x == 0) {
-        const long long S = (long long)n_units * steps_per_unit;
-        const long long u_lo = (long long)unit * steps_per_unit, u_hi = u_lo + steps_per_unit;
-        int w0 = (int)(u_lo * G / S);
-        while (w0 > 0 && ws_range_lo(w0, G, S) > u_lo) --w0;
-        while (w0 + 1 < G && ws_range_lo(w0 + 1, G, S) <= u_lo) ++w0;
-        int n = 0;
-        long long lo = ws_range_lo(w0, G, S);
-        for (int w = w0; w < G && lo < u_hi; ++w) {
-            const long long next = ws_range_lo(w + 1, G, S);
-            if (next > u_lo && next != lo) seg[n++] = w;
-            lo = next;
-        }
-        n_seg = n;
-    }
+    if (threadIdx.x == 0) n_seg = wn_unit_segments(unit, n_units, steps_per_unit, G, seg);
     __syncthreads();
     if (unit >= n_units) return;
     const int off = (int)(e - (long long)unit * SLAB);
@@ -1098,26 +1209,7 @@ wino_wgrad_finish_kernel(const float* __restrict__ red, const WgradGeom wg, floa
     double du[WN_FREQ];
 #pragma unroll
     for (int f = 0; f < WN_FREQ; ++f) du[f] = (double)sl[f * 1024];
-    double t[3][6];     // G^T dU: t[a][j] = sum_i G[i][a] dU[i][j]
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-            double acc = 0.0;
-#pragma unroll
-            for (int i = 0; i < 6; ++i) acc += WN_G[i][a] * du[i * 6 + j];
-            t[a][j] = acc;
-        }
-    float* out = dw + ((size_t)co * cin + ci) * 9;
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) {
-            double acc = 0.0;
-#pragma unroll
-            for (int j = 0; j < 6; ++j) acc += t[a][j] * WN_G[j][b];
-            out[a * 3 + b] = (float)acc;
-        }
+    wn_filter_grad(du, dw + ((size_t)co * cin + ci) * 9);
 }
 
 
@@ -1162,6 +1254,39 @@ extern "C" int toda_conv3x3_transform_weight(const float* w, int cout, int cin, 
     hipLaunchKernelGGL(wino_weight_kernel, dim3(cdiv(threads, WN_BLOCK)), dim3(WN_BLOCK), 0, (hipStream_t)stream, w, cout, cin, mode, u);
     TODA_LAUNCH_CHECK();
     return TODA_OK;
+}
+
+extern "C" int toda_conv3x3_transform_weight_batch(const toda_conv3x3_weight_entry* table, int n, void* stream) {
+    TODA_CHECK_ARG(n >= 0 && (table || n == 0), "conv3x3_transform_weight_batch: null table");
+    WeightBatch b = {};
+    auto flush = [&]() -> int {
+        if (b.n > 0) {
+            hipLaunchKernelGGL(wino_weight_batch_kernel, dim3(b.first_block[b.n]), dim3(WN_BLOCK), 0, (hipStream_t)stream, b);
+            TODA_LAUNCH_CHECK();
+        }
+        b.n = 0;
+        return TODA_OK;
+    };
+    for (int i = 0; i < n; ++i) {
+        const toda_conv3x3_weight_entry& t = table[i];
+        const int cout = t.cout, cin = t.cin, mode = t.mode;
+        TODA_CHECK_ARG(t.w && t.u && mode >= 0 && mode <= 2, "conv3x3_transform_weight_batch: entry %d: null pointer or bad mode", i);
+        const int CO = mode == 1 ? cin : cout, CI = mode == 1 ? cout : cin;
+        TODA_CHECK_ARG(CO % WN_COUT == 0 && CI % WN_KC == 0 && CO > 0 && CI > 0 && (mode != 2 || (CI % WN_COUT == 0)),
+                       "conv3x3_transform_weight_batch: entry %d: produced channels %% 32 and contracted channels %% 8 must be 0 (got %d, %d)", i, CO, CI);
+        const long long threads = 6LL * cout * cin * (mode == 2 ? 2 : 1);
+        TODA_CHECK_ARG(threads * 6 < (1LL << 31), "conv3x3_transform_weight_batch: entry %d: operand above 2^31 elements", i);
+        const long long blocks = cdiv(threads, WN_BLOCK);
+        if (b.n == WB_MAX_LAYERS || (b.n > 0 && b.first_block[b.n] + blocks >= (1LL << 31))) {
+            const int rc = flush();
+            if (rc) return rc;
+        }
+        b.w[b.n] = t.w, b.u[b.n] = t.u, b.cout[b.n] = cout, b.cin[b.n] = cin, b.mode[b.n] = mode;
+        if (b.n == 0) b.first_block[0] = 0;
+        b.first_block[b.n + 1] = b.first_block[b.n] + (unsigned)blocks;
+        ++b.n;
+    }
+    return flush();
 }
 
 extern "C" size_t toda_conv3x3_workspace_bytes(void) {
@@ -1273,7 +1398,14 @@ extern "C" int toda_conv3x3_wgrad(const float* x, const float* dy, int batch, in
     static const int ablate = (TODA_ABLATE && getenv("TODA_WINO_WG_ABLATE")) ? atoi(getenv("TODA_WINO_WG_ABLATE")) : 0;   // measurement builds only
     hipLaunchKernelGGL(wino_wgrad_kernel, dim3(grid), dim3(WS_BLOCK), 0, (hipStream_t)stream, x, dy, wg, (float*)ws, ablate);
     TODA_LAUNCH_CHECK();
-    float* red = (float*)ws + (size_t)(WS_MAX_GRID + wg.n_units) * WG_SLAB_FLOATS;
+    const char* const fold = getenv("TODA_WGRAD_FOLD");      // read per call: the tests compare both routes in one process
+    if (!(fold && !strcmp(fold, "pair"))) {
+        hipLaunchKernelGGL(wino_wgrad_fold_kernel, dim3(wg.n_units * (1024 / WF_PAIRS)), dim3(WN_BLOCK), 0, (hipStream_t)stream,
+                           (const float*)ws, wg, grid, dw);
+        TODA_LAUNCH_CHECK();
+        return TODA_OK;
+    }
+    float* red = (float*)ws + (size_t)(WS_MAX_GRID + wg.n_units) * WG_SLAB_FLOATS;     // used by the two-kernel route only
     hipLaunchKernelGGL(wino_wgrad_reduce_kernel<WG_SLAB_FLOATS>, dim3(cdiv((long long)wg.n_units * WG_SLAB_FLOATS, WN_BLOCK)), dim3(WN_BLOCK), 0,
                        (hipStream_t)stream, (const float*)ws, wg.n_units, wg.steps_per_unit, grid, red);
     TODA_LAUNCH_CHECK();

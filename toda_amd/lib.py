@@ -134,6 +134,7 @@ SIGNATURES = {
     "toda_conv3x3_supported": (_i, [_i, _i, _i, _i, _i]),
     "toda_conv3x3_weight_floats": (_sz, [_i, _i]),
     "toda_conv3x3_transform_weight": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "toda_conv3x3_transform_weight_batch": (_i, [_vp, _i, _vp]),
     "toda_conv3x3_workspace_bytes": (_sz, []),
     "toda_conv3x3_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "toda_conv3x3_wgrad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
@@ -244,3 +245,8 @@ def host_f64(vals):
 
 def hptr(arr):
     return C.cast(arr, C.c_void_p)
+
+
+class Conv3x3WeightEntry(C.Structure):
+    """toda_conv3x3_weight_entry of include/toda.h."""
+    _fields_ = [("w", C.c_void_p), ("cout", C.c_int32), ("cin", C.c_int32), ("mode", C.c_int32), ("reserved", C.c_int32), ("u", C.c_void_p)]

@@ -1291,6 +1291,7 @@ def run_dense_sequential(seq, x):
     after it) to the single-pass kernel (bn2d) on the GPU; any other module, and everything on the CPU, runs as is.  Module tree
     and state_dict are untouched."""
     mods = list(seq)
+    conv3x3_prepack(mods, x)          # the filter transforms of every 3x3 layer below in one launch (no-op when they are current)
     i = 0
     while i < len(mods):
         m = mods[i]
@@ -1298,7 +1299,7 @@ def run_dense_sequential(seq, x):
             x = run_dense_sequential(m, x)
         elif (type(m) is torch.nn.ZeroPad2d and tuple(m.padding) == (1, 1, 1, 1) and i + 1 < len(mods) and type(mods[i + 1]) is torch.nn.Conv2d
               and mods[i + 1].padding == (0, 0) and conv3x3_supported(x, mods[i + 1])):
-            x = conv3x3(x, mods[i + 1].weight, mods[i + 1].bias)      # ZeroPad2d(1) + Conv2d(3x3, padding 0) = one padded convolution
+            x = conv3x3(x, mods[i + 1].weight, mods[i + 1].bias, conv3x3_prepacked(mods[i + 1]))      # ZeroPad2d(1) + Conv2d(3x3, padding 0) = one padded convolution
             i += 2
             continue
         elif (type(m) is torch.nn.ZeroPad2d and tuple(m.padding) == (1, 1, 1, 1) and i + 1 < len(mods) and conv3x3s2_supported(x, mods[i + 1])):
@@ -1308,7 +1309,7 @@ def run_dense_sequential(seq, x):
         elif deconv_supported(x, m):
             x = deconv(x, m.weight, m.stride[0], m.bias)              # up-sampling deblock (kernel = stride)
         elif type(m) is torch.nn.Conv2d and m.padding == (1, 1) and conv3x3_supported(x, m):
-            x = conv3x3(x, m.weight, m.bias)
+            x = conv3x3(x, m.weight, m.bias, conv3x3_prepacked(m))
         elif type(m) is torch.nn.BatchNorm2d and bn2d_supported(x, m):
             relu = i + 1 < len(mods) and type(mods[i + 1]) is torch.nn.ReLU
             x = bn2d(x, m, relu)
@@ -1353,6 +1354,90 @@ def conv3x3_transform_weight(weight, mode):
     return u
 
 
+def conv3x3_transform_weights_batched(items):
+    """items: [(weight [Cout, Cin, 3, 3], mode)] -> what conv3x3_transform_weight returns for each, all written by ONE launch into
+    one allocation (toda_conv3x3_transform_weight_batch): the same bits."""
+    lib = L.load()
+    if not items:
+        return []
+    sizes = [lib.toda_conv3x3_weight_floats(w.shape[0], w.shape[1]) * (2 if mode == 2 else 1) for w, mode in items]
+    flat = torch.empty((sum(sizes),), dtype=torch.float32, device=items[0][0].device)
+    ws = [w.contiguous() for w, _ in items]
+    table = (L.Conv3x3WeightEntry * len(items))()
+    outs, off = [], 0
+    for ent, w, (_, mode), n in zip(table, ws, items, sizes):
+        u = flat[off:off + n]
+        ent.w, ent.cout, ent.cin, ent.mode, ent.u = L.ptr(w), w.shape[0], w.shape[1], int(mode), L.ptr(u)
+        outs.append(u.view(2, n // 2) if mode == 2 else u)
+        off += n
+    L.check(lib.toda_conv3x3_transform_weight_batch(L.hptr(table), len(items), L.stream()), "toda_conv3x3_transform_weight_batch")
+    return outs
+
+
+# Writers that change parameters through raw device pointers (the two-launch optimizer step) leave the tensors' version counters
+# alone; they advance this epoch instead, and the cached filter transforms carry it beside the version counter.
+_WEIGHT_EPOCH = [0]
+
+
+def weights_written_in_place():
+    _WEIGHT_EPOCH[0] += 1
+
+
+def _conv3x3_weight_tag(weight):
+    return weight._version, weight.data_ptr(), _WEIGHT_EPOCH[0]
+
+
+def _conv3x3_stack(mods, dx, out):
+    """The stride-1 3x3 Conv2d modules of a module list (nested Sequentials included) whose channels the Winograd kernels take, each with
+    whether its backward will want dX: the input needs a gradient, or a layer before it in the stack has trainable parameters."""
+    prev = None
+    for m in mods:
+        if isinstance(m, torch.nn.Sequential):
+            dx = _conv3x3_stack(list(m), dx, out)
+        else:
+            if (type(m) is torch.nn.Conv2d and m.kernel_size == (3, 3) and m.stride == (1, 1) and m.dilation == (1, 1) and m.groups == 1
+                    and m.padding_mode == "zeros" and m.in_channels % 32 == 0 and m.out_channels % 32 == 0 and m.in_channels > 0
+                    and (m.padding == (1, 1) or (m.padding == (0, 0) and type(prev) is torch.nn.ZeroPad2d and tuple(prev.padding) == (1, 1, 1, 1)))
+                    and m.weight.is_cuda and m.weight.dtype == torch.float32):
+                out.append((m, dx))
+            if not dx and torch.is_grad_enabled() and isinstance(m, torch.nn.Module) and any(p.requires_grad for p in m.parameters(recurse=False)):
+                dx = True
+        prev = m
+    return dx
+
+
+def conv3x3_prepack(mods, x):
+    """Transform the filters of every stride-1 3x3 layer of the stack `mods` (a module list about to run on x) whose weights changed
+    since their last transform, forward and data-gradient operand, in one kernel launch; the operands are kept on the modules under the
+    weights' version counters (as spconv.prepack does for the sparse layers) and the raw-write epoch.  A lone stale layer transforms for itself in conv3x3.
+    Returns the number of layers transformed."""
+    if DENSE_CONV != "winograd" or not x.is_cuda:
+        return 0
+    stack = []
+    _conv3x3_stack(mods, torch.is_grad_enabled() and x.requires_grad, stack)
+    stale = []
+    for conv, dx in stack:
+        ent = conv.__dict__.get("_wino_u")
+        tag = _conv3x3_weight_tag(conv.weight)
+        if ent is None or ent[0] != tag or (dx and ent[2] is None):
+            stale.append((conv, tag, dx))
+    if len(stale) < 2:
+        return 0
+    with torch.no_grad():
+        us = conv3x3_transform_weights_batched([(conv.weight.detach(), 2 if dx else 0) for conv, _, dx in stale])
+    for (conv, tag, dx), u in zip(stale, us):
+        conv.__dict__["_wino_u"] = (tag, u[0], u[1]) if dx else (tag, u, None)
+    return len(stale)
+
+
+def conv3x3_prepacked(conv):
+    """(forward operand, data-gradient operand or None) of conv3x3_prepack while they match the weights, else None."""
+    ent = conv.__dict__.get("_wino_u")
+    if ent is not None and ent[0] == _conv3x3_weight_tag(conv.weight):
+        return ent[1], ent[2]
+    return None
+
+
 def _conv3x3_workspace(device):
     """Per (device, stream) scratch of the stream-K work split: zeroed once, the kernel leaves its flags zero."""
     key = (device.index, L.stream())
@@ -1377,12 +1462,16 @@ class _Conv3x3(torch.autograd.Function):
     dW = the Winograd-domain wgrad kernel, dB = sum of dY."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias):
+    def forward(ctx, x, weight, bias, pre=None):
         x = x.contiguous()
         need_dx = ctx.needs_input_grad[0]
-        u = conv3x3_transform_weight(weight, 2 if need_dx else 0)      # both operands in one launch when dX will be wanted
-        y = conv3x3_run(x, u[0] if need_dx else u, bias, weight.shape[0])
-        ctx.save_for_backward(x, weight, u[1] if need_dx else None)
+        if pre is not None:                                            # operands of conv3x3_prepack (a missing dX operand is made in backward)
+            u_fwd, u_dgrad = pre
+        else:
+            u = conv3x3_transform_weight(weight, 2 if need_dx else 0)      # both operands in one launch when dX will be wanted
+            u_fwd, u_dgrad = (u[0], u[1]) if need_dx else (u, None)
+        y = conv3x3_run(x, u_fwd, bias, weight.shape[0])
+        ctx.save_for_backward(x, weight, u_dgrad if need_dx else None)
         ctx.has_bias = bias is not None
         return y
 
@@ -1397,7 +1486,7 @@ class _Conv3x3(torch.autograd.Function):
             gw = conv3x3_wgrad(x, gy, weight.shape)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             gb = gy.sum((0, 2, 3))
-        return gx, gw, gb
+        return gx, gw, gb, None
 
 
 def conv3x3_wgrad(x, gy, wshape):
@@ -1412,8 +1501,8 @@ def conv3x3_wgrad(x, gy, wshape):
     return dw
 
 
-def conv3x3(x, weight, bias=None):
-    return _Conv3x3.apply(x, weight, bias)
+def conv3x3(x, weight, bias=None, pre=None):
+    return _Conv3x3.apply(x, weight, bias, pre)
 
 
 # ------------------------------------------- stride-2 3x3 convolution and the transposed-convolution deblocks of the BEV neck

@@ -58,6 +58,7 @@ class BaseBEVBackbone(nn.Module):
         # the deblocks end in BatchNorm2d + ReLU (reference :95-102): on the GPU in training mode those tails write their channels of the
         # concatenated map directly (ops.bn2d_cat), so the deblock is run up to its tail and the cat below never launches
         tails = [ops.bn_relu_tail(d) for d in self.deblocks[:len(self.blocks)]] if (ops.BN2D_CAT and len(self.blocks) > 1 and len(self.deblocks) >= len(self.blocks)) else []
+        ops.conv3x3_prepack(list(self.blocks), x)      # the filter transforms of all levels in one launch instead of one per level
         for lvl, block in enumerate(self.blocks):
             x = ops.run_dense_sequential(block, x)
             data_dict[f"spatial_features_{int(h0 / x.shape[2])}x"] = x

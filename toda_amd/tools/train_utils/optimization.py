@@ -130,6 +130,7 @@ class OneCycleAdam:
             self.step()
             return total
         from toda_amd import lib as L
+        from toda_amd import ops
 
         lib = L.load()
         dev = params[0].device
@@ -205,6 +206,7 @@ class OneCycleAdam:
                                      float(max_norm) if max_norm is not None else 0.0, self._lr, self._mom, self._beta2,
                                      float(self.opt.param_groups[0]["eps"]), float(self.wd), c["count"], L.stream())
         L.check(rc, "toda_clip_adam_step")
+        ops.weights_written_in_place()        # the kernel wrote through raw pointers: no version counter moved
         return norm[0]
 
     def _sync_steps(self):
