@@ -323,7 +323,8 @@ int toda_rows_affine_act(const float* x, const float* scale, const float* shift,
                          float* y, void* stream);
 
 /* Batch statistics -> per-channel mean / invstd / scale / shift, plus nn.BatchNorm1d's
- * running-statistic update (momentum, unbiased running_var).  training == 0: running stats. */
+ * running-statistic update (momentum, unbiased running_var; the biased value for n == 1).  training == 0: running stats.
+ * Training mode with n < 1 is an argument error, as in toda_bn_finalize_partials. */
 int toda_bn_finalize(const double* sums /*[2c] from toda_rows_moments*/, int n, int c,
                      const float* gamma, const float* beta, float* running_mean /*nullable*/,
                      float* running_var /*nullable*/, float momentum, float eps, int training,

@@ -516,6 +516,7 @@ extern "C" int toda_bn_finalize(const double* sums, int n, int c, const float* g
                                 float* mean, float* invstd, float* scale, float* shift, void* stream) {
     TODA_CHECK_ARG(c >= 1 && c <= DN_BLOCK, "bn_finalize: channels must be <= 256 (got %d)", c);
     TODA_CHECK_ARG(training || (running_mean && running_var), "bn_finalize: eval mode needs running statistics");
+    TODA_CHECK_ARG(!training || n >= 1, "bn_finalize: training mode needs rows >= 1 (got %d)", n);
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(1), dim3(DN_BLOCK), 0, (hipStream_t)stream, sums, n, c, gamma, beta,
                        running_mean, running_var, momentum, eps, training, mean, invstd, scale, shift);
     TODA_LAUNCH_CHECK();
