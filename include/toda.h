@@ -604,6 +604,36 @@ int toda_points_world_transform(const float* src, int n, const int32_t* n_dev, i
                                 int rotate, float cosv, float sinv, int rescale, float scale, float* dst,
                                 void* stream);
 
+/* ------------------------------------------------------------------------
+ * Per-object and pyramid augmentations (pcdet/datasets/augmentor/augmentor_utils.py:124-683): the reference's Python loop
+ * over the boxes, each iteration several numpy passes over the cloud, becomes one pass in which a thread carries its
+ * point through every box in order.
+ * ---------------------------------------------------------------------- */
+/* steps: device double [n_steps, 10] rows (cx cy cz dx dy dz rz op p0 p1), in the order the reference visits them; the
+ * box is the one the reference tested (get_points_in_box: 0.1 m margin in local x / y, none in z, borders included, fp32)
+ * and is rounded to fp32.  For every row: walk the steps; where the row's CURRENT x, y, z lie in the step's box - or for
+ * every row when op has bit 16 set - apply op & 15:
+ *   0 / 1 / 2  x / y / z = fp32(fp64(v) + p0)                      3  rotate about z round the box centre, cos = p0, sin = p1 (fp32)
+ *   4          v = (v - centre) * fp32(p0) + centre, v = x, y, z    5 / 6  drop if z >= p0 / z <= p0     7 / 8  drop if y >= p0 / y <= p0
+ * A dropped row takes no further part.  dst rows get the new x, y, z and the other columns copied (dst may alias src;
+ * rows in [min(n, *n_dev), n) are copied unchanged); keep (nullable, int32 [n]): 1 for a surviving valid row, else 0.
+ * The table is staged through LDS in chunks of toda_points_box_steps_chunk() steps, n_steps is unbounded. */
+int toda_points_box_steps_chunk(void);
+int toda_points_box_steps(const float* src, int n, const int32_t* n_dev, int c, const double* steps, int n_steps,
+                          float* dst, int32_t* keep, void* stream);
+/* range_dev[0:2] = min, max of column col over the valid rows; deterministic.  A reduction always has a result: with no
+ * valid row, n == 0 included, it writes (+inf, -inf) (as toda_points_pitch_range; points may be NULL only then).  NaN entries
+ * are skipped (fminf / fmaxf), where numpy's min / max propagate them. */
+size_t toda_points_column_range_workspace_bytes(void);
+int toda_points_column_range(const float* points, int n, const int32_t* n_dev, int c, int col, float* range_dev,
+                             void* ws, size_t ws_bytes, void* stream);
+/* pyramids: device double [np, 5, 3] (apex, four base corners in order round the face: get_pyramids' layout).  A row is
+ * inside when it satisfies the five half-spaces (fp64, faces included) - box_utils.in_hull's answer away from the faces.
+ * bits: uint32 [n, ceil(np / 32)], bit p % 32 of word p / 32 = row in pyramid p (0 for rows beyond *n_dev);
+ * counts: int32 [np], zeroed and filled by the call (integer atomics). */
+int toda_points_in_pyramids(const float* points, int n, const int32_t* n_dev, int c, const double* pyramids, int np,
+                            uint32_t* bits, int32_t* counts, void* stream);
+
 /* Forward convolution that also returns the BatchNorm statistics of its output (reference
  * pcdet/models/backbones_3d/spconv_backbone.py:21-25,54-64: every sparse conv is followed by BatchNorm1d): the
  * per-channel sum and sum of squares are taken from the accumulators in the kernel's epilogue, so the separate

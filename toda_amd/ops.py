@@ -2472,6 +2472,65 @@ def points_world_transform(points, flip_x=False, flip_y=False, rot=None, scale=N
     return out
 
 
+STEP_OPS = {"tx": 0, "ty": 1, "tz": 2, "rot": 3, "scale": 4, "drop_z_ge": 5, "drop_z_le": 6, "drop_y_ge": 7, "drop_y_le": 8}
+STEP_WORLD = 16            # op | STEP_WORLD: the step applies to every row, its box is not tested
+STEP_COLS = 10             # cx cy cz dx dy dz rz op p0 p1
+
+
+def points_box_steps(points, steps, n_dev=None, out=None):
+    """The per-object augmentation chain in one pass (C ABI: toda_points_box_steps).  `steps`: [S, 10] float64 rows
+    (cx cy cz dx dy dz rz op p0 p1; numpy or tensor) in the order the reference's loops visit them.  Returns the new table
+    (a new one unless `out` is given; `out` may be `points`), and the int32 keep flags too when a step drops rows."""
+    lib = L.load()
+    n, c, nd = _rows(points, n_dev)
+    steps = torch.as_tensor(steps, dtype=torch.float64).reshape(-1, STEP_COLS)
+    ops_col = steps[:, 7].to(torch.int64) if steps.device.type == "cpu" else steps[:, 7].cpu().to(torch.int64)
+    if bool(((ops_col & 15) > 8).any()) or bool((ops_col < 0).any()) or bool((ops_col >= 32).any()):
+        raise RuntimeError("points_box_steps: unknown op code")
+    drops = bool(((ops_col & 15) >= 5).any())
+    steps = steps.to(points.device).contiguous()
+    out = torch.empty_like(points) if out is None else out
+    if out.shape != points.shape or out.dtype != points.dtype or not out.is_contiguous():
+        raise RuntimeError("points_box_steps: out must match the table")
+    keep = torch.zeros((n,), dtype=torch.int32, device=points.device) if drops else None
+    rc = lib.toda_points_box_steps(L.ptr(points), n, nd, c, L.ptr(steps) if steps.shape[0] else None, steps.shape[0], L.ptr(out),
+                                   L.ptr(keep) if drops else None, L.stream())
+    L.check(rc, "toda_points_box_steps")
+    return (out, keep) if drops else out
+
+
+def points_column_range(points, col, n_dev=None):
+    """Device float[2]: min and max of column `col` over the valid rows (no host sync)."""
+    lib = L.load()
+    n, c, nd = _rows(points, n_dev)
+    out = torch.empty((2,), dtype=torch.float32, device=points.device)
+    ws_bytes = lib.toda_points_column_range_workspace_bytes()
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=points.device)
+    rc = lib.toda_points_column_range(L.ptr(points), n, nd, c, int(col), L.ptr(out), L.ptr(ws), ws_bytes, L.stream())
+    L.check(rc, "toda_points_column_range")
+    return out
+
+
+def points_in_pyramids(points, pyramids, n_dev=None):
+    """Membership of every row in every pyramid ([P, 5, 3] or [P, 15]: apex + four base corners, get_pyramids' layout).
+    Returns (bits int32 [n, ceil(P / 32)] holding the uint32 words - bit p % 32 of word p // 32 -, counts int32 [P])."""
+    lib = L.load()
+    n, c, nd = _rows(points, n_dev)
+    pyr = torch.as_tensor(pyramids, dtype=torch.float64).reshape(-1, 15).to(points.device).contiguous()
+    p = pyr.shape[0]
+    bits = torch.zeros((n, (p + 31) // 32), dtype=torch.int32, device=points.device)
+    counts = torch.zeros((p,), dtype=torch.int32, device=points.device)
+    if n and p:
+        rc = lib.toda_points_in_pyramids(L.ptr(points), n, nd, c, L.ptr(pyr), p, L.ptr(bits), L.ptr(counts), L.stream())
+        L.check(rc, "toda_points_in_pyramids")
+    return bits, counts
+
+
+def pyramid_bit(bits, p):
+    """Bool [n]: the rows inside pyramid p, from the words of points_in_pyramids."""
+    return ((bits[:, p // 32] >> (p % 32)) & 1).bool()
+
+
 class RowBuffer:
     """A point table under construction on the device: rows are appended by stable selection at a device-side
     cursor, so a whole mix runs without a host round trip; `finish()` reads the row count (one sync)."""
