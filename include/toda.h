@@ -160,7 +160,8 @@ int toda_gridindex_from_coords(const int32_t* idx, int n, const int32_t* n_dev,
  * occupied 32-cell word by the site that set the word's lowest bit), which is all a level whose rows are in
  * caller order needs - rowof[rank] = row, toda_rulebook_subm / toda_rulebook_conv read it as before.  No sweep over
  * the lattice: the bitmap must be all zero on entry (gi_clean != 0: the caller guarantees it, e.g. through
- * toda_gridindex_clear after the previous use; 0: the call clears all of it first). */
+ * toda_gridindex_clear after the previous use; 0: the call clears all of it first).  The coordinates of one list must
+ * be unique: two rows with the same coordinate would race for one rowof entry (spconv never produces such a list). */
 int toda_gridindex_from_coords_unordered(const int32_t* idx, int n, const int32_t* n_dev,
                                          int batch, const int32_t* shape_host,
                                          void* gi, int32_t* rowof, int gi_clean, void* stream);

@@ -710,6 +710,9 @@ static int fill_conv_geom(const char* who, int batch, const int32_t* shape_in, c
                           const int32_t* pd, const int32_t* shape_out, ConvGeom* cg) {
     for (int a = 0; a < 3; ++a) {
         TODA_CHECK_ARG(ks[a] >= 1 && st[a] >= 1 && pd[a] >= 0, "%s: bad kernel/stride/pad on axis %d", who, a);
+        // (C division rounds towards zero: without this an axis one short of its kernel would pass as one output cell)
+        TODA_CHECK_ARG(shape_in[a] + 2 * pd[a] >= ks[a], "%s: axis %d of %d cells (+ 2 * %d) is shorter than the kernel's %d", who, a,
+                       shape_in[a], pd[a], ks[a]);
         const int expect = (shape_in[a] + 2 * pd[a] - ks[a]) / st[a] + 1;
         TODA_CHECK_ARG(shape_out[a] == expect, "%s: shape_out[%d]=%d but (in+2p-k)/s+1=%d", who, a, shape_out[a], expect);
         cg->ks[a] = ks[a];
