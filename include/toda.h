@@ -635,6 +635,18 @@ int toda_points_column_range(const float* points, int n, const int32_t* n_dev, i
 int toda_points_in_pyramids(const float* points, int n, const int32_t* n_dev, int c, const double* pyramids, int np,
                             uint32_t* bits, int32_t* counts, void* stream);
 
+/* Camera field-of-view test of a KITTI frame (csrc/kitti_frame.hip): flags[j] = 1 iff point j projects into the image with
+ * non-negative depth (pcdet/datasets/kitti/kitti_dataset.py get_fov_flag + pcdet/utils/calibration_kitti.py lidar_to_rect /
+ * rect_to_img):
+ *   rect = [x y z 1] . M            M = fp32(V2C^T . R0^T), 4 x 3 row-major, formed on the host in fp32 as the reference forms it
+ *   hom  = [rect 1] . P2^T          u = hom0 / rect_z, v = hom1 / rect_z, depth = hom2 - P2[2][3]      (P2: 3 x 4 row-major)
+ *   flag = 0 <= u < img_w  and  0 <= v < img_h  and  depth >= 0        (fp32; NaN / inf compare false, as in numpy)
+ * Rows, n_dev and flags as in the family above.  m_host and p2_host are host arrays of 12 floats, passed to the kernel by
+ * value: no device upload, no sync.  Rows beyond min(n, *n_dev) are left untouched.  c < 3, n < 0, a null matrix, a
+ * non-positive image size, or null points / flags with n > 0 return -1; n == 0 succeeds without a launch. */
+int toda_points_fov_flags(const float* points, int n, const int32_t* n_dev, int c, const float* m_host,
+                          const float* p2_host, int img_h, int img_w, int32_t* flags, void* stream);
+
 /* Forward convolution that also returns the BatchNorm statistics of its output (reference
  * pcdet/models/backbones_3d/spconv_backbone.py:21-25,54-64: every sparse conv is followed by BatchNorm1d): the
  * per-channel sum and sum of squares are taken from the accumulators in the kernel's epilogue, so the separate

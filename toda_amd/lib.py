@@ -136,6 +136,7 @@ SIGNATURES = {
     "toda_points_column_range_workspace_bytes": (_sz, []),
     "toda_points_column_range": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _sz, _vp]),
     "toda_points_in_pyramids": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "toda_points_fov_flags": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
     "toda_conv3x3_supported": (_i, [_i, _i, _i, _i, _i]),
     "toda_conv3x3_weight_floats": (_sz, [_i, _i]),
     "toda_conv3x3_transform_weight": (_i, [_vp, _i, _i, _i, _vp, _vp]),

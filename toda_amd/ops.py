@@ -2403,6 +2403,20 @@ def points_rect(points, lo_xy, hi_xy, closed=False, n_dev=None):
     return flags
 
 
+def points_fov_flags(points, m, p2, image_shape, n_dev=None):
+    """flags[j] = 1 iff row j projects into the camera image with non-negative depth (C ABI: toda_points_fov_flags).  `m`: the
+    4 x 3 fp32 LiDAR -> rectified-camera matrix and `p2`: the 3 x 4 projection, host arrays (Calibration.fov_matrices());
+    image_shape = (height, width)."""
+    lib = L.load()
+    n, c, nd = _rows(points, n_dev)
+    flags = torch.zeros((n,), dtype=torch.int32, device=points.device)
+    mh, ph = L.host_f32(np.asarray(m, np.float32).reshape(12)), L.host_f32(np.asarray(p2, np.float32).reshape(12))
+    rc = lib.toda_points_fov_flags(L.ptr(points), n, nd, c, L.hptr(mh), L.hptr(ph), int(image_shape[0]), int(image_shape[1]),
+                                   L.ptr(flags), L.stream())
+    L.check(rc, "toda_points_fov_flags")
+    return flags
+
+
 def points_polar_cell(points, phase, yaw_edges, dis_edges, dis_lo, dis_hi, n_dev=None):
     lib = L.load()
     n, c, nd = _rows(points, n_dev)

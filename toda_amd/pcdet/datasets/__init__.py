@@ -1,6 +1,6 @@
-"""Dataset registry and dataloader builder (reference pcdet/datasets/__init__.py:25-97).  Real
-dataset readers (KITTI / nuScenes / Waymo / ...) are out of scope: the registry holds the
-synthetic dataset that exposes the same attributes and the same collate contract."""
+"""Dataset registry and dataloader builder (reference pcdet/datasets/__init__.py:25-97).  KittiDataset reads the KITTI
+object benchmark from disk; the readers of the other real datasets (nuScenes / Waymo / ...) are out of scope, their
+shapes come from the synthetic datasets, which expose the same attributes and the same collate contract."""
 from functools import partial
 
 import torch
@@ -9,12 +9,14 @@ from torch.utils.data import DistributedSampler as _DistributedSampler
 
 from ..utils import common_utils
 from .dataset import DatasetTemplate
+from .kitti.kitti_dataset import KittiDataset
 from .synthetic import SyntheticLidarDataset, SyntheticPairDataset
 from .mixup_dataset import SyntheticMixupPairDataset
 from .two_dataset import SyntheticMixDataset
 
 __all__ = {
     "DatasetTemplate": DatasetTemplate,
+    "KittiDataset": KittiDataset,
     "SyntheticLidarDataset": SyntheticLidarDataset,
     "SyntheticPairDataset": SyntheticPairDataset,
     "SyntheticMixDataset": SyntheticMixDataset,

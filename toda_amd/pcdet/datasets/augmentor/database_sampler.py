@@ -2,7 +2,7 @@
 frames are pasted into the scene when they collide with nothing.
 
 Same config keys (DB_INFO_PATH, PREPARE {filter_by_min_points, filter_by_difficulty}, SAMPLE_GROUPS, NUM_POINT_FEATURES,
-REMOVE_EXTRA_WIDTH, LIMIT_WHOLE_SCENE, DB_DATA_PATH + USE_SHARED_MEMORY), same db_infos.pkl records, same random draws.
+REMOVE_EXTRA_WIDTH, LIMIT_WHOLE_SCENE, DB_DATA_PATH + USE_SHARED_MEMORY, USE_ROAD_PLANE), same db_infos.pkl records, same random draws.
 MI355X layout: object points live in HBM - the packed database (DB_DATA_PATH, the reference's shared-memory array) is
 uploaded once, per-file objects are cached on first use - and a CUDA scene is edited on the device: in-box kernel +
 compaction remove the scene points under the (enlarged) pasted boxes, the objects are shifted to their box centres and
@@ -77,16 +77,33 @@ class DataBaseSampler:
             self._cache[key] = torch.from_numpy(pts).cuda()
         return self._cache[key]
 
+    @staticmethod
+    def put_boxes_on_road_planes(gt_boxes, road_plane, calib):
+        """KITTI only (reference :136-154): lower or lift every pasted box so that its bottom face sits on the frame's road
+        plane (a, b, c, d in the rectified camera frame).  Host numpy on the sampled boxes; returns (boxes, the shift taken off z)."""
+        a, b, c, d = road_plane
+        centre_cam = calib.lidar_to_rect(gt_boxes[:, 0:3])
+        centre_cam[:, 1] = (-d - a * centre_cam[:, 0] - c * centre_cam[:, 2]) / b
+        road_z = calib.rect_to_lidar(centre_cam)[:, 2]
+        mv_height = gt_boxes[:, 2] - gt_boxes[:, 5] / 2 - road_z
+        gt_boxes[:, 2] -= mv_height
+        return gt_boxes, mv_height
+
     def add_sampled_boxes_to_scene(self, data_dict, sampled_gt_boxes, picked):
         mask = data_dict["gt_boxes_mask"]
         gt_boxes, gt_names = data_dict["gt_boxes"][mask], data_dict["gt_names"][mask]
         points = data_dict["points"]
+        mv_height = None
+        if self.sampler_cfg.get("USE_ROAD_PLANE", False) and data_dict.get("road_plane") is not None:      # frames without a plane file: as sampled
+            sampled_gt_boxes, mv_height = self.put_boxes_on_road_planes(sampled_gt_boxes, data_dict["road_plane"], data_dict["calib"])
         is_numpy = isinstance(points, np.ndarray)
         scene = torch.as_tensor(points, dtype=torch.float32).cuda() if not (torch.is_tensor(points) and points.is_cuda) else points
         objs = []
-        for info in picked:
+        for k, info in enumerate(picked):
             obj = self.object_points(info).clone()
             obj[:, :3] += torch.from_numpy(np.asarray(info["box3d_lidar"][:3], np.float32)).to(obj.device)
+            if mv_height is not None:
+                obj[:, 2] -= float(mv_height[k])
             objs.append(obj)
         large = box_utils.enlarge_box3d(sampled_gt_boxes[:, 0:7], extra_width=self.sampler_cfg.REMOVE_EXTRA_WIDTH)
         scene = box_utils.remove_points_in_boxes3d(scene.contiguous(), large)
@@ -126,35 +143,41 @@ class DataBaseSampler:
         return data_dict
 
 
-def create_groundtruth_database(dataset, save_dir, used_classes=None, packed=True):
+def create_groundtruth_database(dataset, save_dir, used_classes=None, packed=True, db_name="gt_database", info_name="dbinfos.pkl",
+                                frame_id=None, extra_info=None):
     """Cut every labelled object out of the dataset's frames (reference nuscenes_dataset.py:370-412 /
     waymo_dataset.py create_groundtruth_database): per object a `<frame>_<class>_<k>.bin` of its points relative to the
     box centre, `dbinfos.pkl` = {class: [{name, path, image_idx, gt_idx, box3d_lidar, num_points_in_gt, difficulty,
     global_data_offset}]} and, with `packed`, all objects in one `gt_database_global.npy` (the shared-memory layout).
-    Membership = index of the first box holding the point (points_in_boxes_gpu)."""
+    Membership = index of the first box holding the point (points_in_boxes_gpu).  A dataset with frame names of its own
+    (KITTI) gives `frame_id(idx)` for the file names and image_idx, `extra_info(idx, i)` for further record fields
+    (difficulty, bbox, score) and the names of the directory and of the infos pickle."""
     from ...ops.roiaware_pool3d import roiaware_pool3d_utils
 
     save_dir = Path(save_dir)
-    db_dir = save_dir / "gt_database"
+    db_dir = save_dir / db_name
     db_dir.mkdir(parents=True, exist_ok=True)
     all_infos, chunks, offset = {}, [], 0
     for idx in range(len(dataset)):
         points, gt_boxes, gt_names = dataset.raw_sample(idx)
         owner = roiaware_pool3d_utils.points_in_boxes_gpu(torch.from_numpy(points[:, 0:3]).unsqueeze(0).float().cuda(),
                                                           torch.from_numpy(gt_boxes[:, 0:7]).unsqueeze(0).float().cuda())[0].cpu().numpy()
+        frame = frame_id(idx) if frame_id is not None else idx
         for i in range(gt_boxes.shape[0]):
             obj = points[owner == i].copy()
             obj[:, :3] -= gt_boxes[i, :3]
-            rel = Path("gt_database") / f"{idx}_{gt_names[i]}_{i}.bin"
+            rel = Path(db_name) / f"{frame}_{gt_names[i]}_{i}.bin"
             obj.astype(np.float32).tofile(str(save_dir / rel))
             if used_classes is None or gt_names[i] in used_classes:
-                info = {"name": gt_names[i], "path": str(rel), "image_idx": idx, "gt_idx": i, "box3d_lidar": gt_boxes[i],
+                info = {"name": gt_names[i], "path": str(rel), "image_idx": frame, "gt_idx": i, "box3d_lidar": gt_boxes[i],
                         "num_points_in_gt": obj.shape[0], "difficulty": 0, "global_data_offset": [offset, offset + obj.shape[0]]}
+                if extra_info is not None:
+                    info.update(extra_info(idx, i))
                 all_infos.setdefault(gt_names[i], []).append(info)
                 chunks.append(obj.astype(np.float32))
                 offset += obj.shape[0]
-    with open(save_dir / "dbinfos.pkl", "wb") as f:
+    with open(save_dir / info_name, "wb") as f:
         pickle.dump(all_infos, f)
     if packed:
-        np.save(str(save_dir / "gt_database_global.npy"), np.concatenate(chunks, 0) if chunks else np.zeros((0, dataset.raw_sample(0)[0].shape[1]), np.float32))
+        np.save(str(save_dir / f"{db_name}_global.npy"), np.concatenate(chunks, 0) if chunks else np.zeros((0, dataset.raw_sample(0)[0].shape[1]), np.float32))
     return all_infos

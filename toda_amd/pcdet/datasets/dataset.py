@@ -62,6 +62,8 @@ class DatasetTemplate(torch_data.Dataset):
             ids = np.array([self.class_names.index(n) + 1 for n in names[keep]], dtype=np.float32).reshape(-1, 1)
             data_dict["gt_boxes"] = np.concatenate([boxes, ids], axis=1).astype(np.float32)
             data_dict["gt_names"] = names[keep]
+            if data_dict.get("gt_boxes2d") is not None:                      # reference :142-143
+                data_dict["gt_boxes2d"] = data_dict["gt_boxes2d"][keep]
         if data_dict.get("points") is not None:
             data_dict = self.point_feature_encoder.forward(data_dict)
         data_dict = self.data_processor.forward(data_dict)
@@ -97,7 +99,7 @@ class DatasetTemplate(torch_data.Dataset):
     @staticmethod
     def collate_batch(batch_list, _unused=False):
         """Concatenate voxels, prepend the batch index to points / voxel_coords, zero-pad gt_boxes
-        to [B, max_gt, 8] (reference :161-233)."""
+        to [B, max_gt, 8] (and gt_boxes2d to [B, max_gt, 4]), keep calib as a list of objects (reference :161-233)."""
         merged = defaultdict(list)
         for sample in batch_list:
             for key, val in sample.items():
@@ -118,7 +120,9 @@ class DatasetTemplate(torch_data.Dataset):
                     ret["points_per_sample"] = [int(v.shape[0]) for v in vals]
             elif key in ("augmentation_list", "augmentation_params"):
                 ret[key] = list(vals)  # per-sample python objects (stage-2 consistency step)
-            elif key == "gt_boxes":
+            elif key == "calib":
+                ret[key] = list(vals)  # per-sample Calibration objects (KittiDataset.generate_prediction_dicts)
+            elif key in ("gt_boxes", "gt_boxes2d"):
                 width = vals[0].shape[-1]
                 out = np.zeros((len(vals), max(len(v) for v in vals), width), dtype=np.float32)
                 for k, v in enumerate(vals):

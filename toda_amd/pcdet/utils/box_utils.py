@@ -1,4 +1,4 @@
-"""Box helpers on the anchor-head path (reference pcdet/utils/box_utils.py:255-298)."""
+"""Box helpers on the anchor-head path and the KITTI camera-frame conversions (reference pcdet/utils/box_utils.py)."""
 import numpy as np
 import torch
 
@@ -76,3 +76,56 @@ def remove_points_in_boxes3d(points, boxes3d):
     if was_cuda:
         return pts
     return pts.cpu().numpy() if is_numpy else pts.cpu()
+
+
+# ---- KITTI camera-frame boxes (reference box_utils.py:92-108, 161-246).  At most a few hundred boxes per frame, and the results
+# are host annotation dicts: numpy, no kernel.
+def boxes3d_kitti_camera_to_lidar(boxes3d_camera, calib):
+    """[N, 7] (x y z l h w ry; rectified camera frame, y at the bottom face) -> (x y z dx dy dz heading), z at the box centre."""
+    cam = np.array(boxes3d_camera, copy=True)
+    xyz = calib.rect_to_lidar(cam[:, 0:3])
+    xyz[:, 2] += cam[:, 4] / 2
+    return np.concatenate([xyz, cam[:, 3:4], cam[:, 5:6], cam[:, 4:5], -(cam[:, 6:7] + np.pi / 2)], axis=-1)
+
+
+def boxes3d_lidar_to_kitti_camera(boxes3d_lidar, calib):
+    """The inverse map: [N, 7] LiDAR boxes -> (x y z l h w ry) in the rectified camera frame."""
+    lidar = np.array(boxes3d_lidar, copy=True)
+    xyz = lidar[:, 0:3]
+    xyz[:, 2] -= lidar[:, 5] / 2
+    return np.concatenate([calib.lidar_to_rect(xyz), lidar[:, 3:4], lidar[:, 5:6], lidar[:, 4:5], -lidar[:, 6:7] - np.pi / 2], axis=-1)
+
+
+def boxes3d_to_corners3d_kitti_camera(boxes3d, bottom_center=True):
+    """[N, 7] camera boxes -> fp32 corners [N, 8, 3]: 0-3 the bottom face (+l+w, +l-w, -l-w, -l+w), 4-7 above them (-y is up);
+    bottom_center: y is the bottom face's height, else the centre's."""
+    n = boxes3d.shape[0]
+    half_l, half_w = boxes3d[:, 3:4] / 2.0, boxes3d[:, 5:6] / 2.0
+    h = boxes3d[:, 4:5]
+    sx = np.array([1, 1, -1, -1, 1, 1, -1, -1], dtype=np.float32)
+    sz = np.array([1, -1, -1, 1, 1, -1, -1, 1], dtype=np.float32)
+    x_local = (half_l * sx).astype(np.float32)
+    z_local = (half_w * sz).astype(np.float32)
+    if bottom_center:
+        y_local = np.zeros((n, 8), dtype=np.float32)
+        y_local[:, 4:8] = -h
+    else:
+        y_local = (h / 2.0 * np.array([1, 1, 1, 1, -1, -1, -1, -1], dtype=np.float32)).astype(np.float32)
+    ry = boxes3d[:, 6]
+    zeros, ones = np.zeros(ry.size, dtype=np.float32), np.ones(ry.size, dtype=np.float32)
+    rot = np.transpose(np.array([[np.cos(ry), zeros, -np.sin(ry)], [zeros, ones, zeros], [np.sin(ry), zeros, np.cos(ry)]]), (2, 0, 1))
+    turned = np.matmul(np.stack([x_local, y_local, z_local], axis=2), rot)
+    return (turned + boxes3d[:, None, 0:3]).astype(np.float32)
+
+
+def boxes3d_kitti_camera_to_imageboxes(boxes3d, calib, image_shape=None):
+    """[N, 7] camera boxes -> [N, 4] (x1 y1 x2 y2): the pixel extent of the eight corners, clipped to the image
+    ([0, width - 1] x [0, height - 1]) when image_shape = (height, width) is given."""
+    corners = boxes3d_to_corners3d_kitti_camera(boxes3d)
+    pixels, _ = calib.rect_to_img(corners.reshape(-1, 3))
+    pixels = pixels.reshape(-1, 8, 2)
+    boxes2d = np.concatenate([pixels.min(axis=1), pixels.max(axis=1)], axis=1)
+    if image_shape is not None:
+        boxes2d[:, 0::2] = np.clip(boxes2d[:, 0::2], a_min=0, a_max=image_shape[1] - 1)
+        boxes2d[:, 1::2] = np.clip(boxes2d[:, 1::2], a_min=0, a_max=image_shape[0] - 1)
+    return boxes2d

@@ -26,6 +26,12 @@ def mask_points_by_range(points, limit_range):
         & (points[:, 1] >= limit_range[1]) & (points[:, 1] <= limit_range[4])
 
 
+def drop_info_with_name(info, name):
+    """Every array of an annotation dict without the entries whose info['name'] equals `name` (KITTI's DontCare)."""
+    keep = [i for i, n in enumerate(info["name"]) if n != name]
+    return {key: val[keep] for key, val in info.items()}
+
+
 def set_random_seed(seed):
     random.seed(seed)
     np.random.seed(seed)
