@@ -647,6 +647,24 @@ int toda_points_in_pyramids(const float* points, int n, const int32_t* n_dev, in
 int toda_points_fov_flags(const float* points, int n, const int32_t* n_dev, int c, const float* m_host,
                           const float* p2_host, int img_h, int img_w, int32_t* flags, void* stream);
 
+/* Multi-sweep merge of a nuScenes sample (csrc/nuscenes_frame.hip; pcdet/datasets/nuscenes/nuscenes_dataset.py get_sweep /
+ * get_lidar_with_sweeps): one pass over the concatenated raw rows of the sample's n_sweeps files, sweep 0 being the key frame.
+ *   rows [n, 5] fp32 (x, y, z, intensity, ring), device; sweep s holds rows offsets_host[s] .. offsets_host[s + 1] - 1
+ *   flags[j] = !(drop_ego[s] && |x| < radius && |y| < radius)       raw fp32 coordinates, strict, a NaN keeps the row
+ *   x' = (float)(((double)x * m[0] + (double)y * m[1] + (double)z * m[2]) + m[3]), y' from m[4..7], z' from m[8..11]
+ *        when has_matrix[s] (m = matrices_host + 12 s, a 3 x 4 row-major double matrix); x, y, z unchanged otherwise
+ *   x', y', z' += shift_host[0..2] in fp32, after that rounding, when shift_host is not null
+ *   out[j] = (x', y', z', intensity, (float)time_lags_host[s])       [n, 5] fp32, written for every row, kept or not
+ * Every *_host argument is a host array (offsets n_sweeps + 1 int32, matrices 12 n_sweeps doubles, has_matrix / drop_ego
+ * n_sweeps int32, time_lags n_sweeps doubles) and reaches the kernel by value: no device upload, no sync.  flags feed
+ * toda_rows_select_append, which keeps the order: key frame, then the sweeps in table order, each in file order.
+ * n < 0, n_sweeps outside 1 .. toda_sweeps_merge_max_sweeps(), a null table, a radius that is negative or NaN, offsets that
+ * do not run from 0 to n without decreasing, or null rows / out / flags with n > 0 return -1; n == 0 succeeds without a launch. */
+int toda_sweeps_merge_max_sweeps(void);
+int toda_sweeps_merge(const float* rows, int n, int n_sweeps, const int32_t* offsets_host, const double* matrices_host,
+                      const int32_t* has_matrix_host, const int32_t* drop_ego_host, const double* time_lags_host,
+                      float radius, const float* shift_host, float* out, int32_t* flags, void* stream);
+
 /* Forward convolution that also returns the BatchNorm statistics of its output (reference
  * pcdet/models/backbones_3d/spconv_backbone.py:21-25,54-64: every sparse conv is followed by BatchNorm1d): the
  * per-channel sum and sum of squares are taken from the accumulators in the kernel's epilogue, so the separate

@@ -2417,6 +2417,33 @@ def points_fov_flags(points, m, p2, image_shape, n_dev=None):
     return flags
 
 
+def sweeps_merge(rows, offsets, matrices, time_lags, drop_ego, radius=1.0, shift=None):
+    """The multi-sweep merge of a nuScenes sample (C ABI: toda_sweeps_merge).  `rows`: [n, 5] fp32 device rows (x, y, z,
+    intensity, ring) of the sample's S files one after the other, sweep s at rows offsets[s] .. offsets[s + 1] - 1.  Host side,
+    per sweep: `matrices[s]` a float64 matrix of 3 or 4 rows x 4 columns into the key frame, or None (rows pass through);
+    `time_lags[s]`; `drop_ego[s]`: flag the rows with |x| < radius and |y| < radius.  `shift`: 3 fp32 values added after the
+    fp32 rounding.  Returns (out [n, 5] fp32: x' y' z' intensity time, flags [n] int32: 1 = keep) for ops.RowBuffer."""
+    lib = L.load()
+    if rows.dim() != 2 or rows.shape[1] != 5 or rows.dtype != torch.float32:
+        raise RuntimeError("sweeps_merge: rows must be [n, 5] float32")
+    n, s = rows.shape[0], len(matrices)
+    if not (len(offsets) == s + 1 and len(time_lags) == s and len(drop_ego) == s):
+        raise RuntimeError("sweeps_merge: offsets, matrices, time_lags and drop_ego disagree on the number of sweeps")
+    mats = np.zeros((max(s, 1), 12), np.float64)
+    for k, m in enumerate(matrices):
+        if m is not None:
+            mats[k] = np.asarray(m, np.float64).reshape(-1, 4)[:3].reshape(12)
+    out = torch.empty((n, 5), dtype=torch.float32, device=rows.device)
+    flags = torch.zeros((n,), dtype=torch.int32, device=rows.device)
+    off, mh = L.host_i32(offsets), L.host_f64(mats.reshape(-1))
+    has, ego, lag = L.host_i32([m is not None for m in matrices]), L.host_i32([bool(d) for d in drop_ego]), L.host_f64(time_lags)
+    sh = L.host_f32(np.asarray(shift, np.float32).reshape(3)) if shift is not None else None
+    rc = lib.toda_sweeps_merge(L.ptr(rows), n, s, L.hptr(off), L.hptr(mh), L.hptr(has), L.hptr(ego), L.hptr(lag), float(radius),
+                               L.hptr(sh) if sh is not None else None, L.ptr(out), L.ptr(flags), L.stream())
+    L.check(rc, "toda_sweeps_merge")
+    return out, flags
+
+
 def points_polar_cell(points, phase, yaw_edges, dis_edges, dis_lo, dis_hi, n_dev=None):
     lib = L.load()
     n, c, nd = _rows(points, n_dev)

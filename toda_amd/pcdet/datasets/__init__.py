@@ -1,6 +1,7 @@
 """Dataset registry and dataloader builder (reference pcdet/datasets/__init__.py:25-97).  KittiDataset reads the KITTI
-object benchmark from disk; the readers of the other real datasets (nuScenes / Waymo / ...) are out of scope, their
-shapes come from the synthetic datasets, which expose the same attributes and the same collate contract."""
+object benchmark and NuScenesDataset the nuScenes sweeps from disk; the readers of the other real datasets (Waymo / ...)
+are out of scope, their shapes come from the synthetic datasets, which expose the same attributes and the same collate
+contract."""
 from functools import partial
 
 import torch
@@ -10,6 +11,7 @@ from torch.utils.data import DistributedSampler as _DistributedSampler
 from ..utils import common_utils
 from .dataset import DatasetTemplate
 from .kitti.kitti_dataset import KittiDataset
+from .nuscenes.nuscenes_dataset import NuScenesDataset
 from .synthetic import SyntheticLidarDataset, SyntheticPairDataset
 from .mixup_dataset import SyntheticMixupPairDataset
 from .two_dataset import SyntheticMixDataset
@@ -17,6 +19,7 @@ from .two_dataset import SyntheticMixDataset
 __all__ = {
     "DatasetTemplate": DatasetTemplate,
     "KittiDataset": KittiDataset,
+    "NuScenesDataset": NuScenesDataset,
     "SyntheticLidarDataset": SyntheticLidarDataset,
     "SyntheticPairDataset": SyntheticPairDataset,
     "SyntheticMixDataset": SyntheticMixDataset,
