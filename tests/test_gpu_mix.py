@@ -125,6 +125,29 @@ def test_range_cut_elevation_test_and_elevation_bands_match_numpy_restatement():
         np.testing.assert_array_equal(ops.points_pitch_band(d, np.float32(-1.8), lo, hi, edges).cpu().numpy(), want)
 
 
+@pytest.mark.parametrize("c", [4, 5])
+@pytest.mark.parametrize("n", [0, 1, 65, 70000])
+def test_pitch_range_at_the_edges(n, c):
+    """toda_points_pitch_range where the column range is tested too: no row, one row, a partial workgroup, and more than 256 x 256
+    rows (the grid-stride loop and all 256 partials), with and without a device-side row count; a cloud with every row within
+    1 m has no valid row and gives (inf, -inf)."""
+    from toda_amd import ops
+
+    def want(p):
+        dis = OM._range32(p[:, 0], p[:, 1])
+        v = OM.pitch32(p[:, 2], dis)[dis > 1]
+        return np.float32([v.min(), v.max()] if len(v) else [np.inf, -np.inf])
+
+    pts, near = cloud(60 + n, n, c), cloud(61 + n, n, c, span=0.7)                  # range <= 0.7 sqrt(2) < 1
+    n_dev = torch.tensor([n // 2], dtype=torch.int32, device="cuda")
+    np.testing.assert_array_equal(ops.points_pitch_range(dev(pts)).cpu().numpy(), want(pts))
+    np.testing.assert_array_equal(ops.points_pitch_range(dev(pts), n_dev).cpu().numpy(), want(pts[: n // 2]))
+    for got in (ops.points_pitch_range(dev(near)), ops.points_pitch_range(dev(near), n_dev)):
+        np.testing.assert_array_equal(got.cpu().numpy(), np.float32([np.inf, -np.inf]))
+    if n >= 65:
+        assert np.isfinite(want(pts)).all() and np.isfinite(want(pts[: n // 2])).all()
+
+
 def test_select_append_is_a_stable_compaction_with_device_side_counts():
     from toda_amd import ops
     a, b = cloud(7, 70001, c=5), cloud(8, 33333, c=5)

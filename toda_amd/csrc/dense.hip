@@ -1,15 +1,15 @@
 // Sparse -> dense scatter (SparseConvTensor.dense() / PointPillarScatter) and the per-channel
 // row statistics / affine+ReLU passes of the BatchNorm1d+ReLU pair, for gfx950.
-// All HBM-bandwidth work.  The scatter moves a [64 rows x 32 channels] tile through LDS so that
+// All HBM-bandwidth work.  The fixed-order fold and the statistics bookkeeping live in bn_fold.cuh.  The scatter moves a [64 rows x 32 channels] tile through LDS so that
 // feature reads are 128-byte row segments and dense writes run along x (consecutive canonical
 // rows are x-neighbours), instead of 4-byte accesses strided by a whole channel plane.
+#include "bn_fold.cuh"
 #include "common.h"
 
 namespace toda {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int DN_BLOCK = 256;
 constexpr int DN_ROWS = 64;
 constexpr int DN_CH = 32;
 
@@ -132,20 +132,12 @@ __device__ __forceinline__ void rows_reduce2(int n, int c, int rows_per_block, L
     }
 }
 
-// sums[col] = sum_g scratch[col][g]: one block per column, strided partial sums then an LDS tree - fixed order
+// sums[col] = sum_g scratch[col][g]: one block per column, in fold_column's fixed order (prototype: bn_fold.cuh)
 __global__ void __launch_bounds__(DN_BLOCK)
 fold_partials_kernel(double* __restrict__ sums, int blocks, int cols) {
     __shared__ double part[DN_BLOCK];
-    const double* src = sums + cols + (size_t)blockIdx.x * blocks;
-    double acc = 0.0;
-    for (int g = threadIdx.x; g < blocks; g += DN_BLOCK) acc += src[g];
-    part[threadIdx.x] = acc;
-    __syncthreads();
-    for (int w = DN_BLOCK / 2; w > 0; w >>= 1) {
-        if (threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) sums[blockIdx.x] = part[0];
+    const double total = fold_column(sums + cols + (size_t)blockIdx.x * blocks, blocks, part);
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
 static inline void reduce_plan(int n, int* blocks, int* rows_per_block) {
@@ -280,21 +272,12 @@ rows_bn_bwd_apply_kernel(const f32x4* __restrict__ dy, const f32x4* __restrict__
 __global__ void __launch_bounds__(DN_BLOCK)
 colsum_fold_kernel(const double* __restrict__ part, int blocks, float* __restrict__ out) {
     __shared__ double sh[DN_BLOCK];
-    const double* src = part + (size_t)blockIdx.x * blocks;
-    double acc = 0.0;
-    for (int g = threadIdx.x; g < blocks; g += DN_BLOCK) acc += src[g];
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int w = DN_BLOCK / 2; w > 0; w >>= 1) {
-        if (threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[blockIdx.x] = (float)sh[0];
+    const double total = fold_column(part + (size_t)blockIdx.x * blocks, blocks, sh);
+    if (threadIdx.x == 0) out[blockIdx.x] = (float)total;
 }
 
-// one block: batch statistics -> (mean, invstd, scale, shift) + running-stat update, exactly
-// nn.BatchNorm1d's training-mode bookkeeping (biased variance for normalisation, unbiased for
-// running_var, running = (1-m)*running + m*batch).  training == 0: use the running statistics.
+// one block: batch statistics -> (mean, invstd, scale, shift) + running-stat update (bn_train_channel).  training == 0: use
+// the running statistics.
 __global__ void __launch_bounds__(DN_BLOCK)
 bn_finalize_kernel(const double* __restrict__ sums, int n, int c, const float* __restrict__ gamma,
                    const float* __restrict__ beta, float* __restrict__ running_mean, float* __restrict__ running_var,
@@ -302,33 +285,16 @@ bn_finalize_kernel(const double* __restrict__ sums, int n, int c, const float* _
                    float* __restrict__ scale_out, float* __restrict__ shift_out) {
     const int ch = threadIdx.x;
     if (ch >= c) return;
-    float mean, var;
-    if (training) {
-        const double m = sums[ch] / (double)n;
-        double v = sums[c + ch] / (double)n - m * m;
-        if (v < 0.0) v = 0.0;
-        mean = (float)m;
-        var = (float)v;
-        if (running_mean) {
-            const double unbiased = n > 1 ? v * (double)n / (double)(n - 1) : v;
-            running_mean[ch] = (1.0f - momentum) * running_mean[ch] + momentum * mean;
-            running_var[ch] = (1.0f - momentum) * running_var[ch] + momentum * (float)unbiased;
-        }
-    } else {
-        mean = running_mean[ch];
-        var = running_var[ch];
-    }
-    const float invstd = 1.0f / sqrtf(var + eps);
-    const float g = gamma ? gamma[ch] : 1.0f, b = beta ? beta[ch] : 0.0f;
-    mean_out[ch] = mean;
-    invstd_out[ch] = invstd;
-    scale_out[ch] = g * invstd;
-    shift_out[ch] = b - mean * g * invstd;
+    if (training)
+        bn_train_channel(ch, sums[ch], sums[c + ch], n, gamma, beta, running_mean, running_var, momentum, eps, mean_out, invstd_out,
+                         scale_out, shift_out);
+    else
+        bn_write_channel(ch, running_mean[ch], running_var[ch], eps, gamma, beta, mean_out, invstd_out, scale_out, shift_out);
 }
 
 // fold_partials_kernel + bn_finalize_kernel in one launch (training mode): block ch folds its two columns of per-workgroup
-// partials (sum and sum of squares of channel ch) with EXACTLY fold_partials_kernel's order - thread-strided partial sums, then the
-// LDS tree - leaves the totals in sums[ch] / sums[c + ch] and finalises the channel.  Saves a launch per BatchNorm1d.
+// partials (sum and sum of squares of channel ch) with fold_column, leaves the totals in sums[ch] / sums[c + ch] and finalises the
+// channel.  Saves a launch per BatchNorm1d.
 __global__ void __launch_bounds__(DN_BLOCK)
 bn_fold_finalize_kernel(double* __restrict__ sums, int blocks, int n, int c, const float* __restrict__ gamma,
                         const float* __restrict__ beta, float* __restrict__ running_mean, float* __restrict__ running_var,
@@ -336,39 +302,14 @@ bn_fold_finalize_kernel(double* __restrict__ sums, int blocks, int n, int c, con
                         float* __restrict__ scale_out, float* __restrict__ shift_out) {
     __shared__ double part[DN_BLOCK];
     const int ch = blockIdx.x;
-    double tot[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const double* src = sums + 2 * c + (size_t)(q * c + ch) * blocks;
-        double acc = 0.0;
-        for (int g = threadIdx.x; g < blocks; g += DN_BLOCK) acc += src[g];
-        part[threadIdx.x] = acc;
-        __syncthreads();
-        for (int w = DN_BLOCK / 2; w > 0; w >>= 1) {
-            if (threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
-            __syncthreads();
-        }
-        tot[q] = part[0];
-        __syncthreads();
-    }
+    const double sum = fold_column(sums + 2 * c + (size_t)ch * blocks, blocks, part);
+    __syncthreads();                                     // every thread has read part[0] before it is written again
+    const double sumsq = fold_column(sums + 2 * c + (size_t)(c + ch) * blocks, blocks, part);
     if (threadIdx.x != 0) return;
-    sums[ch] = tot[0];
-    sums[c + ch] = tot[1];
-    const double m = tot[0] / (double)n;
-    double v = tot[1] / (double)n - m * m;
-    if (v < 0.0) v = 0.0;
-    const float mean = (float)m, var = (float)v;
-    if (running_mean) {
-        const double unbiased = n > 1 ? v * (double)n / (double)(n - 1) : v;
-        running_mean[ch] = (1.0f - momentum) * running_mean[ch] + momentum * mean;
-        running_var[ch] = (1.0f - momentum) * running_var[ch] + momentum * (float)unbiased;
-    }
-    const float invstd = 1.0f / sqrtf(var + eps);
-    const float g = gamma ? gamma[ch] : 1.0f, b = beta ? beta[ch] : 0.0f;
-    mean_out[ch] = mean;
-    invstd_out[ch] = invstd;
-    scale_out[ch] = g * invstd;
-    shift_out[ch] = b - mean * g * invstd;
+    sums[ch] = sum;
+    sums[c + ch] = sumsq;
+    bn_train_channel(ch, sum, sumsq, n, gamma, beta, running_mean, running_var, momentum, eps, mean_out, invstd_out, scale_out,
+                     shift_out);
 }
 
 // grid for the grid-stride elementwise kernels: <= EW_BLOCKS blocks and (blocks * 256 * 4) % c == 0

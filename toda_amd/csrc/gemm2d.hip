@@ -20,8 +20,6 @@
 #include "common.h"
 #include "split_common.cuh"
 
-extern "C" int toda_matrix_path(void);      // spconv.hip: 0 = native fp32 MFMA, 1 = the exact bf16 hi/mid/lo split
-
 namespace toda {
 
 typedef float pg4 __attribute__((ext_vector_type(4)));

@@ -37,8 +37,8 @@ __global__ void __launch_bounds__(PT_BLOCK)
 sweeps_merge_kernel(const float* __restrict__ rows, SweepTable t, float* __restrict__ out, int32_t* __restrict__ flags) {
     const int s = blockIdx.y;
     const int begin = t.offset[s], count = t.offset[s + 1] - begin;
-    const int k = blockIdx.x * PT_BLOCK + threadIdx.x;
-    if (k >= count) return;
+    const int k = pt_row(count, nullptr);
+    if (k < 0) return;
     const size_t j = (size_t)begin + k;
     const float* p = rows + j * SWEEP_IN_COLS;
     float x = p[0], y = p[1], z = p[2];
@@ -68,9 +68,8 @@ extern "C" int toda_sweeps_merge(const float* rows, int n, int n_sweeps, const i
                                  float radius, const float* shift_host, float* out, int32_t* flags, void* stream) {
     TODA_CHECK_ARG(n >= 0, "sweeps_merge: need n >= 0");
     TODA_CHECK_ARG(n_sweeps >= 1 && n_sweeps <= SWEEPS_MAX, "sweeps_merge: %d sweeps, supported are 1 to %d (key frame included)", n_sweeps, SWEEPS_MAX);
-    TODA_CHECK_ARG(offsets_host && matrices_host && has_matrix_host && drop_ego_host && time_lags_host, "sweeps_merge: null sweep table");
     TODA_CHECK_ARG(radius >= 0.f, "sweeps_merge: the ego radius must be a number >= 0");
-    if (n == 0) return TODA_OK;
+    PT_CHECK_TABLES(offsets_host && matrices_host && has_matrix_host && drop_ego_host && time_lags_host, "sweeps_merge: null sweep table");
     TODA_CHECK_ARG(rows && out && flags, "sweeps_merge: null rows, out or flags");
     TODA_CHECK_ARG(offsets_host[0] == 0 && offsets_host[n_sweeps] == n, "sweeps_merge: row offsets must run from 0 to n = %d", n);
     SweepTable t;

@@ -2,8 +2,9 @@
 // random_translation_along_*, random_local_translation_along_*, local_rotation, local_scaling, global / local frustum
 // dropout, local_pyramid_dropout / _sparsify / _swap) for gfx950.  The reference loops over the boxes in Python and runs
 // several full-length numpy passes over the cloud per box; here a point's fate depends only on the point itself and on the
-// box list, so one thread carries one point through every box in order.  All three kernels are single streaming passes
-// over the [n, c] fp32 table (4*n*c bytes in, as much out, plus the membership words of the pyramid test).
+// box list, so one thread carries one point through every box in order.  Both kernels and the column range (a functor of
+// points_common.cuh's pt_range_kernel) are single streaming passes over the [n, c] fp32 table (4*n*c bytes in, as much out,
+// plus the membership words of the pyramid test).
 //
 // Roundings follow the reference's numpy code (file built with -ffp-contract=off): the box test is get_points_in_box
 // (point_in_box<1>) on the point's current coordinates, translation adds in fp64 and rounds once (equal to the fp32 add for an
@@ -34,9 +35,8 @@ __global__ void __launch_bounds__(PT_BLOCK)
 points_box_steps_kernel(const float* src, int n, const int32_t* __restrict__ n_dev, int c, const double* __restrict__ steps,
                         int n_steps, float* dst, int32_t* __restrict__ keep) {   // dst may alias src
     __shared__ StepPre ss[STEP_CHUNK];
-    const int rows = eff_n(n, n_dev);
-    const int j = blockIdx.x * PT_BLOCK + threadIdx.x;
-    const bool active = j < rows;
+    const int j = pt_row(n, nullptr);                     // rows in [min(n, *n_dev), n) are not active
+    const bool active = pt_row(n, n_dev) >= 0;
     float x = 0.f, y = 0.f, z = 0.f;
     if (active) x = src[(size_t)j * c], y = src[(size_t)j * c + 1], z = src[(size_t)j * c + 2];
     bool alive = active;
@@ -86,7 +86,7 @@ points_box_steps_kernel(const float* src, int n, const int32_t* __restrict__ n_d
             }
         }
     }
-    if (j >= n) return;
+    if (j < 0) return;
     const float* p = src + (size_t)j * c;
     float* q = dst + (size_t)j * c;
     if (active) {
@@ -99,39 +99,15 @@ points_box_steps_kernel(const float* src, int n, const int32_t* __restrict__ n_d
     if (keep) keep[j] = alive ? 1 : 0;
 }
 
-// min / max of one column over the valid rows: per-workgroup partials, then one workgroup folds them (the
-// points_pitch_range_kernel scheme - no atomics, nothing to initialise).  No row: (+inf, -inf).  fminf / fmaxf skip a NaN
-// where numpy's min / max hand it on: on a cloud that holds NaN the threshold formed from this range is not numpy's.
-__global__ void __launch_bounds__(PT_BLOCK)
-points_column_range_kernel(const float* __restrict__ pts, int n, const int32_t* __restrict__ n_dev, int c, int col,
-                           const float* __restrict__ partial_in, int n_partial, float* __restrict__ out) {
-    __shared__ float smin[PT_BLOCK / 64], smax[PT_BLOCK / 64];
-    float lo = INFINITY, hi = -INFINITY;
-    if (partial_in) {
-        for (int i = threadIdx.x; i < n_partial; i += PT_BLOCK) {
-            lo = fminf(lo, partial_in[2 * i]);
-            hi = fmaxf(hi, partial_in[2 * i + 1]);
-        }
-    } else {
-        const int rows = eff_n(n, n_dev);
-        for (int j = blockIdx.x * PT_BLOCK + threadIdx.x; j < rows; j += gridDim.x * PT_BLOCK) {
-            const float v = pts[(size_t)j * c + col];
-            lo = fminf(lo, v);
-            hi = fmaxf(hi, v);
-        }
+// the value of pt_range_kernel (points_common.cuh) for a column's min / max: every valid row counts.  On a cloud that holds NaN
+// the threshold formed from this range is not numpy's (fminf / fmaxf skip a NaN).
+struct ColumnOfRow {
+    int col;
+    __device__ bool operator()(const float* __restrict__ p, float& v) const {
+        v = p[col];
+        return true;
     }
-    for (int d = 32; d >= 1; d >>= 1) {
-        lo = fminf(lo, __shfl_xor(lo, d, 64));
-        hi = fmaxf(hi, __shfl_xor(hi, d, 64));
-    }
-    if ((threadIdx.x & 63) == 0) smin[threadIdx.x >> 6] = lo, smax[threadIdx.x >> 6] = hi;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < PT_BLOCK / 64; ++w) lo = fminf(lo, smin[w]), hi = fmaxf(hi, smax[w]);
-        out[2 * blockIdx.x] = lo;
-        out[2 * blockIdx.x + 1] = hi;
-    }
-}
+};
 
 // five half-spaces n . p <= d with outward normals: the four sides through the apex, then the base
 struct PyrPre {
@@ -166,9 +142,8 @@ points_in_pyramids_kernel(const float* __restrict__ pts, int n, const int32_t* _
                           int32_t* __restrict__ counts) {
     __shared__ PyrPre sp[PYR_CHUNK];
     __shared__ int scnt[PYR_CHUNK];
-    const int rows = eff_n(n, n_dev);
-    const int j = blockIdx.x * PT_BLOCK + threadIdx.x;
-    const bool active = j < rows;
+    const int j = pt_row(n, nullptr);                     // rows in [min(n, *n_dev), n) are not active
+    const bool active = pt_row(n, n_dev) >= 0;
     double x = 0.0, y = 0.0, z = 0.0;
     if (active) x = (double)pts[(size_t)j * c], y = (double)pts[(size_t)j * c + 1], z = (double)pts[(size_t)j * c + 2];
     for (int w = 0; w < words; ++w) {
@@ -186,7 +161,7 @@ points_in_pyramids_kernel(const float* __restrict__ pts, int n, const int32_t* _
             const int cnt = __popcll(__ballot(in));
             if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(&scnt[q], cnt);
         }
-        if (j < n) bits[(size_t)j * words + w] = word;
+        if (j >= 0) bits[(size_t)j * words + w] = word;
         __syncthreads();
         if ((int)threadIdx.x < m && scnt[threadIdx.x]) atomicAdd(&counts[w * PYR_CHUNK + threadIdx.x], scnt[threadIdx.x]);
     }
@@ -200,45 +175,30 @@ extern "C" int toda_points_box_steps_chunk(void) { return STEP_CHUNK; }
 
 extern "C" int toda_points_box_steps(const float* src, int n, const int32_t* n_dev, int c, const double* steps, int n_steps,
                                      float* dst, int32_t* keep, void* stream) {
-    TODA_CHECK_ARG(n >= 0 && c >= 3, "points_box_steps: need n >= 0 and at least 3 columns (x, y, z)");
+    PT_CHECK_SIZES("points_box_steps");
     TODA_CHECK_ARG(n_steps >= 0, "points_box_steps: n_steps >= 0");
-    hipStream_t s = (hipStream_t)stream;
-    if (n == 0) return TODA_OK;
-    TODA_CHECK_ARG(src && dst && (steps || n_steps == 0), "points_box_steps: null table");
-    hipLaunchKernelGGL(points_box_steps_kernel, dim3(cdiv(n, PT_BLOCK)), dim3(PT_BLOCK), 0, s, src, n, n_dev, c, steps, n_steps, dst, keep);
+    PT_CHECK_TABLES(src && dst && (steps || n_steps == 0), "points_box_steps: null table");
+    hipLaunchKernelGGL(points_box_steps_kernel, dim3(cdiv(n, PT_BLOCK)), dim3(PT_BLOCK), 0, (hipStream_t)stream, src, n, n_dev, c, steps,
+                       n_steps, dst, keep);
     TODA_LAUNCH_CHECK();
     return TODA_OK;
 }
 
-constexpr int PL_RANGE_BLOCKS = 256;
-
-extern "C" size_t toda_points_column_range_workspace_bytes(void) { return (size_t)PL_RANGE_BLOCKS * 2 * sizeof(float); }
+extern "C" size_t toda_points_column_range_workspace_bytes(void) { return pt_range_workspace_bytes(); }
 
 extern "C" int toda_points_column_range(const float* points, int n, const int32_t* n_dev, int c, int col, float* range_dev,
                                         void* ws, size_t ws_bytes, void* stream) {
     TODA_CHECK_ARG(n >= 0 && c >= 1 && col >= 0 && col < c, "points_column_range: need n >= 0 and a column in [0, c)");
-    hipStream_t s = (hipStream_t)stream;
-    if (ws_bytes < toda_points_column_range_workspace_bytes()) {
-        set_error("points_column_range: workspace %zu < required %zu", ws_bytes, toda_points_column_range_workspace_bytes());
-        return TODA_EWORKSPACE;
-    }
-    // a reduction always has a result: n == 0 still writes (+inf, -inf), so only the table may be null then
-    TODA_CHECK_ARG((points || n == 0) && range_dev && ws, "points_column_range: null table, result or workspace");
-    const int blocks = n > 0 ? (cdiv(n, PT_BLOCK) < PL_RANGE_BLOCKS ? cdiv(n, PT_BLOCK) : PL_RANGE_BLOCKS) : 1;
-    float* partial = (float*)ws;
-    hipLaunchKernelGGL(points_column_range_kernel, dim3(blocks), dim3(PT_BLOCK), 0, s, points, n, n_dev, c, col, (const float*)nullptr, 0, partial);
-    hipLaunchKernelGGL(points_column_range_kernel, dim3(1), dim3(PT_BLOCK), 0, s, points, n, n_dev, c, col, (const float*)partial, blocks, range_dev);
-    TODA_LAUNCH_CHECK();
-    return TODA_OK;
+    return pt_range_pass("points_column_range", points, n, n_dev, c, ColumnOfRow{col}, range_dev, ws, ws_bytes, stream);
 }
 
 extern "C" int toda_points_in_pyramids(const float* points, int n, const int32_t* n_dev, int c, const double* pyramids, int np,
                                        uint32_t* bits, int32_t* counts, void* stream) {
-    TODA_CHECK_ARG(n >= 0 && c >= 3, "points_in_pyramids: need n >= 0 and at least 3 columns (x, y, z)");
+    PT_CHECK_SIZES("points_in_pyramids");
     TODA_CHECK_ARG(np >= 0, "points_in_pyramids: pyramid count >= 0");
+    if (np == 0) return TODA_OK;
+    PT_CHECK_TABLES(points && pyramids && bits && counts, "points_in_pyramids: null table");
     hipStream_t s = (hipStream_t)stream;
-    if (n == 0 || np == 0) return TODA_OK;
-    TODA_CHECK_ARG(points && pyramids && bits && counts, "points_in_pyramids: null table");
     TODA_HIP(hipMemsetAsync(counts, 0, (size_t)np * sizeof(int32_t), s));
     hipLaunchKernelGGL(points_in_pyramids_kernel, dim3(cdiv(n, PT_BLOCK)), dim3(PT_BLOCK), 0, s, points, n, n_dev, c, pyramids, np,
                        cdiv(np, PYR_CHUNK), bits, counts);

@@ -26,6 +26,7 @@
 #include <mutex>
 #include <vector>
 
+#include "bn_fold.cuh"
 #include "common.h"
 
 
@@ -1376,7 +1377,6 @@ extern "C" int toda_timing_end(float* ms_out, int cap, int* n_out) {
 }
 
 namespace toda {
-__global__ void fold_partials_kernel(double* __restrict__ sums, int blocks, int cols);   // dense.hip
 static bool gg_stats_supported(int c_gather, int c_produce) {
     const int Q = tiles_pow2(c_gather), NT = tiles_pow2(c_produce);
     return (c_gather & 3) == 0 && Q >= 2 && NT >= Q && Q * NT <= 32 && !(Q == 8 && NT == 8) && c_produce % 4 == 0 && c_produce == 16 * NT;

@@ -2370,51 +2370,53 @@ def _rows(points, n_dev):
     return points.shape[0], points.shape[1], (L.ptr(n_dev) if n_dev is not None else None)
 
 
-def points_in_boxes(points, boxes, mode=0, n_dev=None):
-    """flags[j] = 1 iff some box holds point j (mode 0: roiaware points_in_boxes_cpu test, mode 1: get_points_in_box)."""
+def _row_pass(name, points, n_dev, fill, *args):
+    """A pass with one int32 per row: allocate the result holding `fill` (what rows past n_dev keep), call the C entry point
+    `name`(points, n, n_dev, c, *args, result, stream), check it."""
+    n, c, nd = _rows(points, n_dev)
+    out = torch.full((n,), fill, dtype=torch.int32, device=points.device)
+    L.check(getattr(L.load(), name)(L.ptr(points), n, nd, c, *args, L.ptr(out), L.stream()), name)
+    return out
+
+
+def _row_range(name, points, n_dev, *args):
+    """A range reduction: device float[2] (min, max) from the C entry point `name`(points, n, n_dev, c, *args, result, ws,
+    ws_bytes, stream) with the workspace of `name`_workspace_bytes()."""
     lib = L.load()
     n, c, nd = _rows(points, n_dev)
-    flags = torch.full((n,), -1 if mode == 2 else 0, dtype=torch.int32, device=points.device)   # mode 2: first box index
+    out = torch.empty((2,), dtype=torch.float32, device=points.device)
+    ws_bytes = getattr(lib, name + "_workspace_bytes")()
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=points.device)
+    L.check(getattr(lib, name)(L.ptr(points), n, nd, c, *args, L.ptr(out), L.ptr(ws), ws_bytes, L.stream()), name)
+    return out
+
+
+def points_in_boxes(points, boxes, mode=0, n_dev=None):
+    """flags[j] = 1 iff some box holds point j (mode 0: roiaware points_in_boxes_cpu test, mode 1: get_points_in_box)."""
+    fill = -1 if mode == 2 else 0                                                               # mode 2: first box index
     k = int(boxes.shape[0]) if boxes is not None and boxes.dim() == 2 else 0
+    n = _rows(points, n_dev)[0]
     if n == 0 or k == 0:
-        return flags
+        return torch.full((n,), fill, dtype=torch.int32, device=points.device)
     boxes = boxes.contiguous().float()
-    rc = lib.toda_points_in_boxes(L.ptr(points), n, nd, c, L.ptr(boxes), k, boxes.shape[1], int(mode), L.ptr(flags), L.stream())
-    L.check(rc, "toda_points_in_boxes")
-    return flags
+    return _row_pass("toda_points_in_boxes", points, n_dev, fill, L.ptr(boxes), k, boxes.shape[1], int(mode))
 
 
 def points_sector(points, lo, hi, n_dev=None):
-    lib = L.load()
-    n, c, nd = _rows(points, n_dev)
-    flags = torch.zeros((n,), dtype=torch.int32, device=points.device)
-    rc = lib.toda_points_sector(L.ptr(points), n, nd, c, float(lo), float(hi), L.ptr(flags), L.stream())
-    L.check(rc, "toda_points_sector")
-    return flags
+    return _row_pass("toda_points_sector", points, n_dev, 0, float(lo), float(hi))
 
 
 def points_rect(points, lo_xy, hi_xy, closed=False, n_dev=None):
-    lib = L.load()
-    n, c, nd = _rows(points, n_dev)
-    flags = torch.zeros((n,), dtype=torch.int32, device=points.device)
     lo, hi = L.host_f64(lo_xy), L.host_f64(hi_xy)
-    rc = lib.toda_points_rect(L.ptr(points), n, nd, c, L.hptr(lo), L.hptr(hi), int(bool(closed)), L.ptr(flags), L.stream())
-    L.check(rc, "toda_points_rect")
-    return flags
+    return _row_pass("toda_points_rect", points, n_dev, 0, L.hptr(lo), L.hptr(hi), int(bool(closed)))
 
 
 def points_fov_flags(points, m, p2, image_shape, n_dev=None):
     """flags[j] = 1 iff row j projects into the camera image with non-negative depth (C ABI: toda_points_fov_flags).  `m`: the
     4 x 3 fp32 LiDAR -> rectified-camera matrix and `p2`: the 3 x 4 projection, host arrays (Calibration.fov_matrices());
     image_shape = (height, width)."""
-    lib = L.load()
-    n, c, nd = _rows(points, n_dev)
-    flags = torch.zeros((n,), dtype=torch.int32, device=points.device)
     mh, ph = L.host_f32(np.asarray(m, np.float32).reshape(12)), L.host_f32(np.asarray(p2, np.float32).reshape(12))
-    rc = lib.toda_points_fov_flags(L.ptr(points), n, nd, c, L.hptr(mh), L.hptr(ph), int(image_shape[0]), int(image_shape[1]),
-                                   L.ptr(flags), L.stream())
-    L.check(rc, "toda_points_fov_flags")
-    return flags
+    return _row_pass("toda_points_fov_flags", points, n_dev, 0, L.hptr(mh), L.hptr(ph), int(image_shape[0]), int(image_shape[1]))
 
 
 def sweeps_merge(rows, offsets, matrices, time_lags, drop_ego, radius=1.0, shift=None):
@@ -2445,51 +2447,28 @@ def sweeps_merge(rows, offsets, matrices, time_lags, drop_ego, radius=1.0, shift
 
 
 def points_polar_cell(points, phase, yaw_edges, dis_edges, dis_lo, dis_hi, n_dev=None):
-    lib = L.load()
-    n, c, nd = _rows(points, n_dev)
-    cell = torch.full((n,), -1, dtype=torch.int32, device=points.device)
     ye, de = L.host_f64(yaw_edges), L.host_f64(dis_edges)
-    rc = lib.toda_points_polar_cell(L.ptr(points), n, nd, c, float(phase), L.hptr(ye), len(yaw_edges) - 1, L.hptr(de),
-                                    len(dis_edges) - 1, float(dis_lo), float(dis_hi), L.ptr(cell), L.stream())
-    L.check(rc, "toda_points_polar_cell")
-    return cell
+    return _row_pass("toda_points_polar_cell", points, n_dev, -1, float(phase), L.hptr(ye), len(yaw_edges) - 1, L.hptr(de),
+                     len(dis_edges) - 1, float(dis_lo), float(dis_hi))
 
 
 def points_polar_select(points, lo, hi, outside=False, dis_mode=0, dis_th=0.0, pitch_range=None, n_dev=None):
     """flags of PolarMix's richer sector tests (C ABI: toda_points_polar_select): yaw inside (lo, hi) or - `outside` - beyond it,
     optionally cut at a range (dis_mode 1: nearer than dis_th, 2: farther) and / or kept only where the elevation lies outside
     `pitch_range` (device float[2] from points_pitch_range)."""
-    lib = L.load()
-    n, c, nd = _rows(points, n_dev)
-    flags = torch.zeros((n,), dtype=torch.int32, device=points.device)
-    rc = lib.toda_points_polar_select(L.ptr(points), n, nd, c, float(lo), float(hi), 2 if outside else 1, int(dis_mode), float(dis_th),
-                                      L.ptr(pitch_range) if pitch_range is not None else None, L.ptr(flags), L.stream())
-    L.check(rc, "toda_points_polar_select")
-    return flags
+    return _row_pass("toda_points_polar_select", points, n_dev, 0, float(lo), float(hi), 2 if outside else 1, int(dis_mode), float(dis_th),
+                     L.ptr(pitch_range) if pitch_range is not None else None)
 
 
 def points_pitch_range(points, n_dev=None):
     """Device float[2]: min and max of -atan2(z, range) over the rows beyond 1 m of range (no host sync)."""
-    lib = L.load()
-    n, c, nd = _rows(points, n_dev)
-    out = torch.empty((2,), dtype=torch.float32, device=points.device)
-    ws_bytes = lib.toda_points_pitch_range_workspace_bytes()
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=points.device)
-    rc = lib.toda_points_pitch_range(L.ptr(points), n, nd, c, L.ptr(out), L.ptr(ws), ws_bytes, L.stream())
-    L.check(rc, "toda_points_pitch_range")
-    return out
+    return _row_range("toda_points_pitch_range", points, n_dev)
 
 
 def points_pitch_band(points, z_offset, clip_lo, clip_hi, edges, n_dev=None):
     """Elevation band of every row (spherical LaserMix): `edges` descending, radians; -1 outside every band."""
-    lib = L.load()
-    n, c, nd = _rows(points, n_dev)
-    band = torch.full((n,), -1, dtype=torch.int32, device=points.device)
     ed = L.host_f64(edges)
-    rc = lib.toda_points_pitch_band(L.ptr(points), n, nd, c, float(z_offset), float(clip_lo), float(clip_hi), L.hptr(ed), len(edges) - 1,
-                                    L.ptr(band), L.stream())
-    L.check(rc, "toda_points_pitch_band")
-    return band
+    return _row_pass("toda_points_pitch_band", points, n_dev, -1, float(z_offset), float(clip_lo), float(clip_hi), L.hptr(ed), len(edges) - 1)
 
 
 def points_rotate_z(points, cosv, sinv, n_dev=None):
@@ -2542,14 +2521,7 @@ def points_box_steps(points, steps, n_dev=None, out=None):
 
 def points_column_range(points, col, n_dev=None):
     """Device float[2]: min and max of column `col` over the valid rows (no host sync)."""
-    lib = L.load()
-    n, c, nd = _rows(points, n_dev)
-    out = torch.empty((2,), dtype=torch.float32, device=points.device)
-    ws_bytes = lib.toda_points_column_range_workspace_bytes()
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=points.device)
-    rc = lib.toda_points_column_range(L.ptr(points), n, nd, c, int(col), L.ptr(out), L.ptr(ws), ws_bytes, L.stream())
-    L.check(rc, "toda_points_column_range")
-    return out
+    return _row_range("toda_points_column_range", points, n_dev, int(col))
 
 
 def points_in_pyramids(points, pyramids, n_dev=None):
