@@ -665,6 +665,16 @@ int toda_sweeps_merge(const float* rows, int n, int n_sweeps, const int32_t* off
                       const int32_t* has_matrix_host, const int32_t* drop_ego_host, const double* time_lags_host,
                       float radius, const float* shift_host, float* out, int32_t* flags, void* stream);
 
+/* Point pass of a processed Waymo frame (csrc/waymo_frame.hip; pcdet/datasets/waymo/waymo_dataset.py get_lidar):
+ *   rows [n, c_in] fp32, device, c_in >= 6: x, y, z, intensity, elongation, NLZ flag (further columns are not read)
+ *   out[j]   = (x, y, z, (float)tanh((double)intensity), elongation)  [n, 5] fp32, written for every row, kept or not; the fp64
+ *              routine rounded once: the sign of zero stays, a NaN passes, large values give +-1
+ *   flags[j] = use_nlz ? row[5] == -1.0f : 1                            int32; a NaN or a neighbour of -1 gives 0; with
+ *              use_nlz == 0 column 5 is not read
+ * flags feed toda_rows_select_append, which keeps the file order.  n < 0, c_in < 6, or null rows / out / flags with n > 0 return
+ * -1; n == 0 succeeds without a launch. */
+int toda_waymo_frame(const float* rows, int n, int c_in, int use_nlz, float* out, int32_t* flags, void* stream);
+
 /* Forward convolution that also returns the BatchNorm statistics of its output (reference
  * pcdet/models/backbones_3d/spconv_backbone.py:21-25,54-64: every sparse conv is followed by BatchNorm1d): the
  * per-channel sum and sum of squares are taken from the accumulators in the kernel's epilogue, so the separate

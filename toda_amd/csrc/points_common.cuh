@@ -1,4 +1,4 @@
-// What the point-table kernels of points.hip, points_local.hip, kitti_frame.hip and nuscenes_frame.hip share: the block size,
+// What the point-table kernels of points.hip, points_local.hip, kitti_frame.hip, nuscenes_frame.hip and waymo_frame.hip share: the block size,
 // the thread -> row map, the argument rule of their entry points, the generic row pass and range reduction (a new pass is a
 // functor with its arithmetic and nothing else), and the point-in-box tests.
 #pragma once

@@ -2446,6 +2446,21 @@ def sweeps_merge(rows, offsets, matrices, time_lags, drop_ego, radius=1.0, shift
     return out, flags
 
 
+def waymo_frame(rows, use_nlz=True):
+    """The point pass of a processed Waymo frame (C ABI: toda_waymo_frame).  `rows`: [n, c_in >= 6] fp32 device rows (x, y, z,
+    intensity, elongation, NLZ flag, ...).  Returns (out [n, 5] fp32: x y z tanh(intensity) elongation, flags [n] int32: 1 = keep,
+    i.e. NLZ flag == -1, or every row with use_nlz false) for ops.RowBuffer."""
+    if not torch.is_tensor(rows) or not rows.is_cuda:
+        raise RuntimeError("waymo_frame: rows must be a device tensor")
+    if rows.dim() != 2 or rows.dtype != torch.float32 or not rows.is_contiguous():
+        raise RuntimeError("waymo_frame: rows must be contiguous [n, c_in] float32")
+    n, c_in = rows.shape
+    out = torch.empty((n, 5), dtype=torch.float32, device=rows.device)
+    flags = torch.empty((n,), dtype=torch.int32, device=rows.device)
+    L.check(L.load().toda_waymo_frame(L.ptr(rows), n, c_in, int(bool(use_nlz)), L.ptr(out), L.ptr(flags), L.stream()), "toda_waymo_frame")
+    return out, flags
+
+
 def points_polar_cell(points, phase, yaw_edges, dis_edges, dis_lo, dis_hi, n_dev=None):
     ye, de = L.host_f64(yaw_edges), L.host_f64(dis_edges)
     return _row_pass("toda_points_polar_cell", points, n_dev, -1, float(phase), L.hptr(ye), len(yaw_edges) - 1, L.hptr(de),

@@ -1,7 +1,7 @@
 """Dataset registry and dataloader builder (reference pcdet/datasets/__init__.py:25-97).  KittiDataset reads the KITTI
-object benchmark and NuScenesDataset the nuScenes sweeps from disk; the readers of the other real datasets (Waymo / ...)
-are out of scope, their shapes come from the synthetic datasets, which expose the same attributes and the same collate
-contract."""
+object benchmark, NuScenesDataset the nuScenes sweeps and WaymoDataset the processed Waymo frames from disk, and
+WaymoNusMixDataset mixes the last two for TODA stage 1; the readers of the other real datasets (Lyft / ...) are out of scope,
+their shapes come from the synthetic datasets, which expose the same attributes and the same collate contract."""
 from functools import partial
 
 import torch
@@ -14,12 +14,18 @@ from .kitti.kitti_dataset import KittiDataset
 from .nuscenes.nuscenes_dataset import NuScenesDataset
 from .synthetic import SyntheticLidarDataset, SyntheticPairDataset
 from .mixup_dataset import SyntheticMixupPairDataset
-from .two_dataset import SyntheticMixDataset
+from .two_dataset import SyntheticMixDataset, WaymoNusMixDataset
+from .waymo.waymo_dataset import WaymoDataset
 
 __all__ = {
     "DatasetTemplate": DatasetTemplate,
     "KittiDataset": KittiDataset,
     "NuScenesDataset": NuScenesDataset,
+    "WaymoDataset": WaymoDataset,
+    "WaymoNusMixDataset": WaymoNusMixDataset,
+    "WaymoNusPolarMixDataset": WaymoNusMixDataset,           # the reference's three names: MIX_TYPE decides which mix runs
+    "WaymoNusCutMixDataset": WaymoNusMixDataset,
+    "WaymoNusLaserMixDataset": WaymoNusMixDataset,
     "SyntheticLidarDataset": SyntheticLidarDataset,
     "SyntheticPairDataset": SyntheticPairDataset,
     "SyntheticMixDataset": SyntheticMixDataset,

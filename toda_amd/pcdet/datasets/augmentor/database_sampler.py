@@ -144,14 +144,15 @@ class DataBaseSampler:
 
 
 def create_groundtruth_database(dataset, save_dir, used_classes=None, packed=True, db_name="gt_database", info_name="dbinfos.pkl",
-                                frame_id=None, extra_info=None):
+                                frame_id=None, extra_info=None, files_for_used_only=False):
     """Cut every labelled object out of the dataset's frames (reference nuscenes_dataset.py:370-412 /
     waymo_dataset.py create_groundtruth_database): per object a `<frame>_<class>_<k>.bin` of its points relative to the
     box centre, `dbinfos.pkl` = {class: [{name, path, image_idx, gt_idx, box3d_lidar, num_points_in_gt, difficulty,
     global_data_offset}]} and, with `packed`, all objects in one `gt_database_global.npy` (the shared-memory layout).
     Membership = index of the first box holding the point (points_in_boxes_gpu).  A dataset with frame names of its own
     (KITTI) gives `frame_id(idx)` for the file names and image_idx, `extra_info(idx, i)` for further record fields
-    (difficulty, bbox, score) and the names of the directory and of the infos pickle."""
+    (difficulty, bbox, score) and the names of the directory and of the infos pickle.  `files_for_used_only`: an object of a
+    class outside `used_classes` gets no .bin file either (Waymo)."""
     from ...ops.roiaware_pool3d import roiaware_pool3d_utils
 
     save_dir = Path(save_dir)
@@ -167,7 +168,8 @@ def create_groundtruth_database(dataset, save_dir, used_classes=None, packed=Tru
             obj = points[owner == i].copy()
             obj[:, :3] -= gt_boxes[i, :3]
             rel = Path(db_name) / f"{frame}_{gt_names[i]}_{i}.bin"
-            obj.astype(np.float32).tofile(str(save_dir / rel))
+            if not files_for_used_only or used_classes is None or gt_names[i] in used_classes:
+                obj.astype(np.float32).tofile(str(save_dir / rel))
             if used_classes is None or gt_names[i] in used_classes:
                 info = {"name": gt_names[i], "path": str(rel), "image_idx": frame, "gt_idx": i, "box3d_lidar": gt_boxes[i],
                         "num_points_in_gt": obj.shape[0], "difficulty": 0, "global_data_offset": [offset, offset + obj.shape[0]]}

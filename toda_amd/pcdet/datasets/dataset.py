@@ -92,7 +92,7 @@ class DatasetTemplate(torch_data.Dataset):
 
     def evaluation(self, det_annos, class_names, **kwargs):
         """A dataset with ground truth in `self.infos` reports here: the KITTI AP table for eval_metric "kitti"
-        (datasets/kitti/kitti_object_eval_python; the nuScenes / Waymo evaluators are out of scope), else BEV-centre-distance
+        (datasets/kitti/kitti_object_eval_python; the nuScenes devkit and Waymo Open Dataset evaluators are out of scope), else BEV-centre-distance
         recall / precision."""
         return "", {}
 

@@ -155,9 +155,9 @@ class NuScenesDataset(DatasetTemplate):
             return len(self.infos) * self.total_epochs
         return len(self.infos)
 
-    def __getitem__(self, index):
-        if self._merge_all_iters_to_one_epoch:
-            index = index % len(self.infos)
+    def raw_frame(self, index):
+        """Sample `index` before prepare_data: {points (SHIFT_COOR added), frame_id, metadata} and, with annotations, gt_names /
+        gt_boxes [n, 9] (FILTER_MIN_POINTS_IN_GT applied, SHIFT_COOR added)."""
         info = copy.deepcopy(self.infos[index])
         shift = np.array(self.shift_coor, dtype=np.float32) if self.shift_coor else None
         if self.on_device:
@@ -173,6 +173,12 @@ class NuScenesDataset(DatasetTemplate):
             data["gt_names"], data["gt_boxes"] = info["gt_names"][keep], info["gt_boxes"][keep]
             if self.shift_coor:
                 data["gt_boxes"][:, 0:3] += self.shift_coor
+        return data
+
+    def __getitem__(self, index):
+        if self._merge_all_iters_to_one_epoch:
+            index = index % len(self.infos)
+        data = self.raw_frame(index)
         data = self.prepare_data(data)
         if "gt_boxes" in data:
             if self.dataset_cfg.get("SET_NAN_VELOCITY_TO_ZEROS", False):

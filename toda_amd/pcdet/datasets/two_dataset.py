@@ -12,7 +12,13 @@ Config keys (as in the reference YAMLs, e.g. tools/cfgs/stage1_targetmix/*.yaml)
   waymo_nus_lasermix_dataset.py:153) = probability of a mixed sample, POLARMIX_DEGREE, POLARMIX_RC_NUM, POLARMIX_UPDATE_METHOD,
   POLARMIX_DIS (FULL | RAND), POLARMIX_USE_PITCH, LASERMIX_NUM_AREAS, LASERMIX_NUM_ANGLES (absent: the spherical variant,
   tools/cfgs/stage1_lasermix/*_pp01.yaml), LASERMIX_PITCH_ANGLE
-  SYNTHETIC: {SOURCE_KIND, TARGET_KIND, NUM_SOURCE, NUM_TARGET, SEED}   (no real dataset on the box)
+  SYNTHETIC: {SOURCE_KIND, TARGET_KIND, NUM_SOURCE, NUM_TARGET, SEED}   (SyntheticMixDataset: no real dataset on the box)
+  WaymoDataset: {...}, NuScenesDataset: {...}                             (WaymoNusMixDataset: the two domains' own dataset
+  configs, each with CLASS_NAMES and DATA_AUGMENTOR, as the reference's stage-1 YAMLs write them)
+
+WaymoNusMixDataset is the dataset those YAMLs name (WaymoNusPolarMixDataset / ...CutMix... / ...LaserMix...: one class here,
+MIX_TYPE decides): source frames from a WaymoDataset, target frames from a NuScenesDataset, both read from disk.  Not built:
+DATA_CONFIG_TEST (evaluate through tools.test on a plain NuScenesDataset yaml) and the stage-2 real mixup datasets.
 """
 import numpy as np
 import torch
@@ -26,15 +32,11 @@ from .processor.inter_domain_point_pseudomix import inter_domain_point_pseudobac
 from .synthetic import synth_cloud
 
 
-class SyntheticMixDataset(DatasetTemplate):
+class MixDatasetTemplate(DatasetTemplate):
+    """What the two-domain datasets share: the mix settings of the config and the MIX_TYPE switch."""
+
     def __init__(self, dataset_cfg, class_names, training=True, root_path=None, logger=None):
         super().__init__(dataset_cfg=dataset_cfg, class_names=class_names, training=training, root_path=root_path, logger=logger)
-        syn = dataset_cfg.get("SYNTHETIC", AttrDict())
-        self.source_kind, self.target_kind = syn.get("SOURCE_KIND", "waymo_toda"), syn.get("TARGET_KIND", "nuscenes_toda")
-        self.num_source, self.num_target = int(syn.get("NUM_SOURCE", 32)), int(syn.get("NUM_TARGET", 32))
-        self.seed = int(syn.get("SEED", 0))
-        self.num_points = {self.source_kind: syn.get("NUM_POINTS_SOURCE", None), self.target_kind: syn.get("NUM_POINTS_TARGET", None)}
-        self.on_device = bool(dataset_cfg.get("MIX_ON_DEVICE", True))
         self.mix_type = dataset_cfg.get("MIX_TYPE", "polarmix")
         if self.mix_type not in ("polarmix", "cutmix", "cutpolarmix", "lasermix", "pseudobbox", "pseudobackground"):
             raise NotImplementedError(self.mix_type)
@@ -52,16 +54,47 @@ class SyntheticMixDataset(DatasetTemplate):
         self.laser_pitch_angle = dataset_cfg.get("LASERMIX_PITCH_ANGLE", [-20, 0])
         self.laser_num_areas = dataset_cfg.get("LASERMIX_NUM_AREAS", 3)
         self.laser_num_angles = dataset_cfg.get("LASERMIX_NUM_ANGLES", None)
-        # keep generated frames: True = resident on the device, "host" = points in pinned host memory, uploaded at every access
-        self.cache_frames = dataset_cfg.get("CACHE_FRAMES", False)
-        self._cache = {}
         self.train_percent = 0.0          # the trainer moves it from 0 to 1 (reference train_utils: cur_it / total_it)
-
-    def __len__(self):
-        return self.num_source + self.num_target
 
     def set_train_percent(self, value):
         self.train_percent = float(value)
+
+    def mix(self, source, target):
+        """The MIX_TYPE switch of the reference's prepare_data (two_dataset.py:227-268)."""
+        kind = self.mix_type
+        if kind == "cutpolarmix":
+            kind = "cutmix" if np.random.random() < 0.5 else "polarmix"
+        if kind == "cutmix":
+            return inter_domain_point_cutmix(source, target, self.point_cloud_range, self.mix_inc_method)
+        if kind == "polarmix":
+            return inter_domain_point_polarmix(source, target, self.polarmix_rot_copy_num, self.polarmix_degree, self.train_percent,
+                                               self.polarmix_update_method, self.point_cloud_range, self.polarmix_dis,
+                                               self.mix_inc_method, self.polarmix_use_pitch)
+        if kind == "lasermix":
+            return inter_domain_point_lasermix(source, target, self.laser_pitch_angle, self.laser_num_areas, self.laser_num_angles,
+                                               self.point_cloud_range, self.mix_inc_method)
+        if kind == "pseudobbox":
+            return inter_domain_point_pseudobbox(source, target)
+        if kind == "pseudobackground":
+            return inter_domain_point_pseudobackground(source, target)
+        raise NotImplementedError(kind)
+
+
+class SyntheticMixDataset(MixDatasetTemplate):
+    def __init__(self, dataset_cfg, class_names, training=True, root_path=None, logger=None):
+        super().__init__(dataset_cfg=dataset_cfg, class_names=class_names, training=training, root_path=root_path, logger=logger)
+        syn = dataset_cfg.get("SYNTHETIC", AttrDict())
+        self.source_kind, self.target_kind = syn.get("SOURCE_KIND", "waymo_toda"), syn.get("TARGET_KIND", "nuscenes_toda")
+        self.num_source, self.num_target = int(syn.get("NUM_SOURCE", 32)), int(syn.get("NUM_TARGET", 32))
+        self.seed = int(syn.get("SEED", 0))
+        self.num_points = {self.source_kind: syn.get("NUM_POINTS_SOURCE", None), self.target_kind: syn.get("NUM_POINTS_TARGET", None)}
+        self.on_device = bool(dataset_cfg.get("MIX_ON_DEVICE", True))
+        # keep generated frames: True = resident on the device, "host" = points in pinned host memory, uploaded at every access
+        self.cache_frames = dataset_cfg.get("CACHE_FRAMES", False)
+        self._cache = {}
+
+    def __len__(self):
+        return self.num_source + self.num_target
 
     # ---- one domain's frame: raw points (+ upload), boxes with the class-id column, encoded features
     def _frame(self, kind, index):
@@ -90,26 +123,6 @@ class SyntheticMixDataset(DatasetTemplate):
                 "gt_boxes": np.concatenate([boxes[keep], ids], axis=1).astype(np.float32), "frame_id": f"{kind}_{index:06d}"}
         return self.point_feature_encoder.forward(data)
 
-    def mix(self, source, target):
-        """The MIX_TYPE switch of the reference's prepare_data (two_dataset.py:227-268)."""
-        kind = self.mix_type
-        if kind == "cutpolarmix":
-            kind = "cutmix" if np.random.random() < 0.5 else "polarmix"
-        if kind == "cutmix":
-            return inter_domain_point_cutmix(source, target, self.point_cloud_range, self.mix_inc_method)
-        if kind == "polarmix":
-            return inter_domain_point_polarmix(source, target, self.polarmix_rot_copy_num, self.polarmix_degree, self.train_percent,
-                                               self.polarmix_update_method, self.point_cloud_range, self.polarmix_dis,
-                                               self.mix_inc_method, self.polarmix_use_pitch)
-        if kind == "lasermix":
-            return inter_domain_point_lasermix(source, target, self.laser_pitch_angle, self.laser_num_areas, self.laser_num_angles,
-                                               self.point_cloud_range, self.mix_inc_method)
-        if kind == "pseudobbox":
-            return inter_domain_point_pseudobbox(source, target)
-        if kind == "pseudobackground":
-            return inter_domain_point_pseudobackground(source, target)
-        raise NotImplementedError(kind)
-
     def __getitem__(self, index):
         if np.random.random(1) < self.mix_prob:
             source = self._frame(self.source_kind, index % self.num_source)
@@ -125,4 +138,89 @@ class SyntheticMixDataset(DatasetTemplate):
         data = self.data_processor.forward(data)
         if self.training and len(data["gt_boxes"]) == 0:
             return self[np.random.randint(len(self))]
+        return data
+
+
+class WaymoNusMixDataset(MixDatasetTemplate):
+    """The real two-domain dataset of stage 1: source frames from a WaymoDataset, target frames from a NuScenesDataset, each
+    built from its sub-block of DATA_CONFIG (own DATA_PATH, CLASS_NAMES and DATA_AUGMENTOR); the joint POINT_FEATURE_ENCODING
+    and DATA_PROCESSOR apply to both domains (reference mix_dataset/waymo_nus_*_dataset.py + two_dataset.py:100-296)."""
+    on_device = True
+
+    def __init__(self, dataset_cfg, class_names, training=True, root_path=None, logger=None):
+        from .nuscenes.nuscenes_dataset import NuScenesDataset
+        from .waymo.waymo_dataset import WaymoDataset
+        super().__init__(dataset_cfg=dataset_cfg, class_names=class_names, training=training, root_path=None, logger=logger)
+        src_cfg, tgt_cfg = dataset_cfg["WaymoDataset"], dataset_cfg["NuScenesDataset"]
+        self.source = WaymoDataset(src_cfg, src_cfg.CLASS_NAMES, training=training, logger=logger)
+        self.target = NuScenesDataset(tgt_cfg, tgt_cfg.CLASS_NAMES, training=training, logger=logger)
+
+    @property
+    def num_source(self):
+        return len(self.source.infos)
+
+    @property
+    def num_target(self):
+        return len(self.target.infos)
+
+    def __len__(self):
+        if self._merge_all_iters_to_one_epoch:
+            return (self.num_source + self.num_target) * self.total_epochs
+        return self.num_source + self.num_target
+
+    # ---- one domain's frame as the mix takes it: augmented by the domain's own augmentor, boxes [n, 7] + the class id of the
+    # domain's own list, the domain's first class under the joint first name, features encoded by the joint encoder
+    def source_frame(self, index):
+        data = self.source.raw_frame(index)
+        data.pop("num_points_in_gt", None)
+        if "gt_boxes" in data:
+            data["gt_boxes"] = data["gt_boxes"][:, 0:7]
+        return self._prepare_domain(self.source, data)
+
+    def target_frame(self, index):
+        data = self.target.raw_frame(index)
+        cfg = self.target.dataset_cfg
+        if "gt_boxes" in data:
+            if cfg.get("SHIFT_COOR", None):
+                data["shift_coor"] = cfg.SHIFT_COOR
+            if cfg.get("SET_NAN_VELOCITY_TO_ZEROS", False):
+                data["gt_boxes"][np.isnan(data["gt_boxes"])] = 0
+            data["gt_boxes"] = data["gt_boxes"][:, 0:7]             # the joint head has no velocity target
+        return self._prepare_domain(self.target, data)
+
+    def _prepare_domain(self, domain, data):
+        names_of = domain.class_names
+        if self.training:
+            assert "gt_boxes" in data, "gt_boxes should be provided for training"
+            if domain.data_augmentor is not None:
+                mask = np.array([n in names_of for n in data["gt_names"]], dtype=bool)
+                data = domain.data_augmentor.forward({**data, "gt_boxes_mask": mask})
+        if data.get("gt_boxes") is not None:
+            names = data["gt_names"]
+            keep = np.array([n in names_of for n in names], dtype=bool)
+            ids = np.array([names_of.index(n) + 1 for n in names[keep]], dtype=np.float32).reshape(-1, 1)
+            data["gt_boxes"] = np.concatenate([data["gt_boxes"][keep], ids], axis=1).astype(np.float32)
+            data["gt_names"] = np.array([self.class_names[0] if n == names_of[0] else n for n in names[keep]], dtype=str)
+        if not torch.is_tensor(data["points"]):                     # MAX_SWEEPS 1: the key frame came from the host route
+            data["points"] = torch.from_numpy(np.ascontiguousarray(data["points"], dtype=np.float32))
+        data["points"] = data["points"].cuda()
+        return self.point_feature_encoder.forward(data)
+
+    def __getitem__(self, index):
+        if self._merge_all_iters_to_one_epoch:
+            index = index % (self.num_source + self.num_target)     # the reference multiplies here, which leaves the range
+        if np.random.random(1) < self.mix_prob:
+            source = self.source_frame(index % self.num_source)
+            target = self.target_frame(index % self.num_target)
+            data = self.mix(source, target)
+            if data["gt_boxes"].ndim != 2:                               # reference two_dataset.py:271-273: draw another sample
+                return self[np.random.randint(len(self))]
+        elif index < self.num_source:
+            data = self.source_frame(index)
+        else:
+            data = self.target_frame(index - self.num_source)
+        data = self.data_processor.forward(data)
+        if self.training and len(data["gt_boxes"]) == 0:
+            return self[np.random.randint(len(self))]
+        data.pop("gt_names", None)
         return data

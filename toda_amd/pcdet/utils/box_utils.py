@@ -88,6 +88,14 @@ def boxes3d_kitti_camera_to_lidar(boxes3d_camera, calib):
     return np.concatenate([xyz, cam[:, 3:4], cam[:, 5:6], cam[:, 4:5], -(cam[:, 6:7] + np.pi / 2)], axis=-1)
 
 
+def boxes3d_kitti_fakelidar_to_lidar(boxes3d_fakelidar):
+    """[N, 7+] (x y z w l h r; the older LiDAR layout, z at the bottom face) -> (x y z dx dy dz heading), z at the box centre
+    (reference box_utils.py:111-125); columns past the seventh are dropped, as there."""
+    old = np.array(boxes3d_fakelidar, copy=True)
+    old[:, 2] += old[:, 5] / 2
+    return np.concatenate([old[:, 0:3], old[:, 4:5], old[:, 3:4], old[:, 5:6], -(old[:, 6:7] + np.pi / 2)], axis=-1)
+
+
 def boxes3d_lidar_to_kitti_camera(boxes3d_lidar, calib):
     """The inverse map: [N, 7] LiDAR boxes -> (x y z l h w ry) in the rectified camera frame."""
     lidar = np.array(boxes3d_lidar, copy=True)
