@@ -3,7 +3,8 @@ conv_transpose2d in float64:
   * the pixel-GEMMs of gemm2d.hip (stride-2 conv, deconv s = 1, 2) under BOTH matrix paths in one process: every kernel variant
     (native 64 / 128, split, the stride-2 data gradient's parity classes), fast and slow accessors, every weight-gradient split regime;
   * the Winograd F(4x4,3x3) stream-K forward / data gradient / weight gradient of conv2d.hip at its tile, grid, gang and unit edges,
-    the two full-size neck shapes, the workspace invariants and the TODA_WINO_VARIANT=0 kernel;
+    the two full-size neck shapes, the workspace invariants, the TODA_WINO_VARIANT=0 kernel and the output transform the two
+    forward kernels share;
   * the narrow output convolutions of conv2d_narrow.hip at their limits, and the torch fallback beyond them.
 Which route each case takes is restated in tests/conv2d_routes.py; tests/test_conv2d_routes.py checks on the CPU that the case lists
 below reach every route.  Routes are asserted only on a 256-CU device; values are compared everywhere.  Every case runs twice and must
@@ -374,6 +375,41 @@ def test_winograd_variant0_fallback_at_the_edges():
     assert p.returncode == 0, p.stderr[-2000:]
     worst = json.loads(p.stdout.strip().split("WORST")[-1])
     assert worst["y"] < WINO_TOL["y"] and worst["dx"] < WINO_TOL["dx"], worst
+
+
+_EPILOGUE_CHILD = r"""
+import sys, json, torch
+sys.path.insert(0, sys.argv[1])
+from tests.test_gpu_conv2d_edges import _epilogue_outputs
+torch.save(_epilogue_outputs(json.loads(sys.argv[2])), sys.argv[3])
+"""
+# (b, cin, cout, h, w): a ragged two-column row, rows of six columns (a full and a half tile), the 16-byte store
+EPILOGUE_CASES = [(1, 8, 32, 1, 2), (2, 8, 64, 5, 6), (3, 8, 32, 8, 8)]
+
+
+def _epilogue_outputs(cases):
+    """y of toda_conv3x3_fwd with bias on 8 input channels (the raw entry point takes Cin % 8), on the CPU."""
+    from toda_amd import ops
+
+    out = []
+    for shape in cases:
+        x, wt, bias, _ = _wino_inputs(tuple(shape), sum(shape))
+        out.append(ops.conv3x3_run(x, ops.conv3x3_transform_weight(wt, 0), bias, shape[2]).cpu())
+    return out
+
+
+def test_winograd_both_forward_kernels_share_one_output_transform(tmp_path):
+    """With 8 input channels a unit is one chunk: no stream-K hand-off, the same MFMA order in wino_fwd_ws_kernel and in the
+    TODA_WINO_VARIANT=0 kernel (a child), and one output transform with bias behind both: the same bits."""
+    import json
+
+    out = str(tmp_path / "variant0.pt")
+    p = subprocess.run([sys.executable, "-c", _EPILOGUE_CHILD, ROOT, json.dumps(EPILOGUE_CASES), out],
+                       env=dict(os.environ, TODA_WINO_VARIANT="0"), capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    for shape, y, y0 in zip(EPILOGUE_CASES, _epilogue_outputs(EPILOGUE_CASES), torch.load(out)):
+        assert y.shape == (shape[0], shape[2], shape[3], shape[4]) and bool(y.abs().sum() > 0), shape
+        assert torch.equal(y, y0), (shape, float((y - y0).abs().max()))
 
 
 # ------------------------------------------------------------------------------------------------------------ narrow convs

@@ -39,6 +39,9 @@ __device__ __forceinline__ void fault_raise(unsigned* word, unsigned bit) {
     if (word) __hip_atomic_fetch_or(word, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// compute units of the current device, cached per device; 256 (an MI355X) with toda_last_error set when the query fails
+int cu_count();
+
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 

@@ -16,6 +16,22 @@ void set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
+int cu_count() {
+    constexpr int MAX_DEV = 64;
+    static int cached[MAX_DEV] = {0};
+    int dev = 0, cus = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess && dev >= 0 && dev < MAX_DEV && cached[dev] > 0) return cached[dev];
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e != hipSuccess || cus <= 0) {
+        set_error("cu_count: device query failed: %s; assuming 256 compute units", hipGetErrorString(e));
+        (void)hipGetLastError();
+        return 256;
+    }
+    if (dev >= 0 && dev < MAX_DEV) cached[dev] = cus;
+    return cus;
+}
+
 // ---- device fault word ------------------------------------------------------------------------------------------------
 // The two kernels whose workgroups wait for each other inside one launch (bn2d_*_split_kernel, wino_fwd_ws_kernel) bound
 // their spins: a wait that outlives FAULT_SPIN_LIMIT polls raises a word in host-mapped pinned memory and falls through

@@ -20,13 +20,18 @@
 // rms error 8.8e-7 against 1.6e-7 for a direct fp32 convolution at Cin = 128).
 // dgrad is the same kernel on the 180-degree-rotated, channel-transposed filters (wino_weight_kernel mode 1).
 // wgrad contracts over TILES in the Winograd domain (dU[f] = dM[f]^T V[f], dM = A dY A^T, V = B^T d B) and maps back with
-// dg = G^T dU G (wino_wgrad_kernel + wino_wgrad_finish_kernel; slabs + fixed-order fold: deterministic, no float atomics).
+// dg = G^T dU G (wino_wgrad_kernel + wino_wgrad_fold_kernel, which folds the slabs in a fixed order and applies G^T . G: deterministic,
+// no float atomics; TODA_WGRAD_FOLD=pair runs the fold as wino_wgrad_reduce_kernel + wino_wgrad_finish_kernel instead).
+// The two persistent kernels (wino_fwd_ws_kernel, wino_wgrad_kernel) are one machine on two operand pairs: they share the stream-K walk
+// (ws_cursor), the consumers' chunk step (wn_consume_chunk) and the producers' pipeline (wn_produce_stream).
 //
 // Replaces torch.nn.Conv2d -> MIOpen for: pcdet/models/backbones_2d/base_bev_backbone.py:37-58,81-112 and
 // pcdet/models/dense_heads/center_head.py:20-28,73-80 (reference paths).
 #include <hip/hip_ext.h>
 #include <stdlib.h>
 #include <string.h>
+
+#include <algorithm>
 
 #include "common.h"
 
@@ -364,36 +369,65 @@ __device__ __forceinline__ void wn_input_transform_store(const Patch& d, float* 
 // CONSECUTIVE tiles, so one store instruction writes 64 contiguous bytes per channel and image row.
 __device__ __forceinline__ int wn_row_of_tile(int t) { return 4 * (t & 3) + (t >> 2); }
 
+constexpr int WS_SLAB_FLOATS = WN_COUT * WN_TILES * 16;      // one unit's outputs: [wave][channel n][row i][quad tile][4]
+
 // Output transform + store of one wave's 16 tiles x 16 channels: lane = (channel n = lane & 15, quad q = lane >> 4),
-// accumulator register r = tile 4 r + q of the group (wn_row_of_tile).
-__device__ __forceinline__ void wn_epilogue(const f32x4 (&acc)[WN_FREQ], float* __restrict__ y, const float* __restrict__ bias,
-                                            int tile_base, int co, const WinoGeom& g, int lane) {
-    const float bv = bias ? bias[co] : 0.0f;
+// accumulator register r = tile 4 r + q of the group (wn_row_of_tile).  Three endings, the last two for a stream-K segment of
+// wino_fwd_ws_kernel (wino_fwd_kernel has no slabs: slab_out = null, n_in = 0):
+//   slab_out != null            contributor: partial sums -> slab (no bias), then publish
+//   else                        add the n_in contributor slabs slab_in + k * stride (k = 0 .. n_in - 1, in order), bias, store y
+// Slab element of (lane n, quad q, register r, row i): ((n * 4 + i) * 4 + r) * 16 + q * 4 .. +3 inside the wave's quarter:
+// the four quads of a store instruction write 64 contiguous bytes.
+__device__ __forceinline__ void ws_epilogue(const f32x4 (&acc)[WN_FREQ], float* __restrict__ y, const float* __restrict__ bias,
+                                            int tile_base, int co, const WinoGeom& g, int lane, float* __restrict__ slab_out,
+                                            const float* __restrict__ slab_in, int n_in, size_t slab_stride) {
+    const float bv = (bias && !slab_out) ? bias[co] : 0.0f;
     const bool vec4 = (g.W & 3) == 0;      // image rows 16-byte aligned: one 16-byte store per tile row
+    const int n = lane & 15, q = lane >> 4;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        const int tile = tile_base + 4 * r + (lane >> 4);
-        if (tile >= g.n_tiles) continue;
-        const int b = tile / g.tiles_img, rem = tile - b * g.tiles_img;
-        const int ty = rem / g.tiles_x, tx = rem - ty * g.tiles_x;
+        const int tile = tile_base + 4 * r + q;
         float tmp[4][6];
 #pragma unroll
         for (int j = 0; j < 6; ++j)
             wn_at(acc[0 * 6 + j][r], acc[1 * 6 + j][r], acc[2 * 6 + j][r], acc[3 * 6 + j][r], acc[4 * 6 + j][r], acc[5 * 6 + j][r],
                   tmp[0][j], tmp[1][j], tmp[2][j], tmp[3][j]);
-        float* const row0 = y + (((size_t)b * g.Cout + co) * g.H + 4 * ty) * g.W + 4 * tx;
-        const bool right = 4 * tx + 3 < g.W;
+        f32x4 o[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             float o0, o1, o2, o3;
             wn_at(tmp[i][0], tmp[i][1], tmp[i][2], tmp[i][3], tmp[i][4], tmp[i][5], o0, o1, o2, o3);
+            o[i] = f32x4{o0, o1, o2, o3};
+        }
+        if (slab_out) {
+            // write-through (sc1) stores: the bytes leave this XCD's L2 without an L2-wide release fence (a buffer_wbl2 per
+            // publishing wave wrote back every dirty line of the XCD - the other workgroups' output rows included)
+            const __amdgpu_buffer_rsrc_t sr = wn_rsrc(slab_out, (unsigned)(WS_SLAB_FLOATS / 4) * 4u);
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4w, o[i]), sr, (unsigned)(((n * 4 + i) * 4 + r) * 16 + q * 4) * 4u, 0, 16);
+            continue;
+        }
+        for (int k = 0; k < n_in; ++k) {
+            const float* sl = slab_in + (size_t)k * slab_stride;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) o[i] += *reinterpret_cast<const f32x4*>(sl + ((n * 4 + i) * 4 + r) * 16 + q * 4);
+        }
+        if (tile >= g.n_tiles) continue;
+        const int b = tile / g.tiles_img, rem = tile - b * g.tiles_img;
+        const int ty = rem / g.tiles_x, tx = rem - ty * g.tiles_x;
+        float* const row0 = y + (((size_t)b * g.Cout + co) * g.H + 4 * ty) * g.W + 4 * tx;
+        const bool right = 4 * tx + 3 < g.W;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
             if (4 * ty + i < g.H) {
                 float* p = row0 + (size_t)i * g.W;
+                const f32x4 v = o[i] + f32x4{bv, bv, bv, bv};
                 if (vec4) {
-                    *reinterpret_cast<f32x4*>(p) = f32x4{o0 + bv, o1 + bv, o2 + bv, o3 + bv};
+                    *reinterpret_cast<f32x4*>(p) = v;
                 } else {
-                    *reinterpret_cast<f32x2*>(p) = f32x2{o0 + bv, o1 + bv};
-                    if (right) *reinterpret_cast<f32x2*>(p + 2) = f32x2{o2 + bv, o3 + bv};
+                    *reinterpret_cast<f32x2*>(p) = f32x2{v[0], v[1]};
+                    if (right) *reinterpret_cast<f32x2*>(p + 2) = f32x2{v[2], v[3]};
                 }
             }
         }
@@ -454,7 +488,7 @@ wino_fwd_kernel(const float* __restrict__ x, const float* __restrict__ u, const 
         __syncthreads();
     }
 
-    wn_epilogue(acc, y, bias, tile0 + wt * 16, cb * WN_COUT + wc * 16 + (lane & 15), g, lane);
+    ws_epilogue(acc, y, bias, tile0 + wt * 16, cb * WN_COUT + wc * 16 + (lane & 15), g, lane, nullptr, nullptr, 0, 0);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -482,71 +516,90 @@ constexpr int WS_BLOCK = 512;
 constexpr size_t WS_FLAG_BYTES = 4096;   // WS_MAX_GRID x 4 ints, at the start of the workspace
 constexpr int WS_MAX_GRID = 256;    // workgroups (= slabs) at most: one per CU of an MI355X
 
+__device__ __forceinline__ long long ws_range_lo(int w, int G, long long S) { return (long long)w * S / G; }
+
+// The stream-K walk of both persistent kernels: step s of the sequence is chunk s % steps_per_unit of unit s / steps_per_unit
+// (ws_cursor), and the segment of a range that ends at hi runs from there to the end of the unit or of the range (ws_segment_end) -
+// the cuts wn_unit_segments lists per unit.  to_scalar: the producers' start.  (64-bit division runs on the vector ALU: hand the
+// wave-uniform results back to scalar registers, or every use as a scalar operand - the loads' soffset - becomes a waterfall loop)
 struct WinoCursor {
     int unit, chunk;
 };
-constexpr int WS_SLAB_FLOATS = WN_COUT * WN_TILES * 16;      // one unit's outputs: [wave][channel n][row i][quad tile][4]
+__device__ __forceinline__ WinoCursor ws_cursor(long long s, int steps_per_unit, bool to_scalar = false) {
+    int unit = (int)(s / steps_per_unit);
+    if (to_scalar) unit = __builtin_amdgcn_readfirstlane(unit);
+    int chunk = (int)(s - (long long)unit * steps_per_unit);
+    if (to_scalar) chunk = __builtin_amdgcn_readfirstlane(chunk);
+    return {unit, chunk};
+}
+__device__ __forceinline__ int ws_segment_end(long long s, long long hi, int chunk, int steps_per_unit) {
+    return (hi - s < steps_per_unit - chunk) ? chunk + (int)(hi - s) : steps_per_unit;
+}
 
-__device__ __forceinline__ long long ws_range_lo(int w, int G, long long S) { return (long long)w * S / G; }
+// One chunk of a consumer wave: the 36 A and B fragments of the images at a_img / b_img, four MFMAs per frequency pair.
+// Fragment reads as inline-asm ds_read_b64 with a counted lgkmcnt: left to itself hipcc fuses the 8-byte reads of
+// two frequencies into ds_read2st64_b64, which moves the same bytes at HALF the LDS rate (128 instead of 256
+// B/clk, MI355X_MICROARCH.md LDS table) - with 72 fragment reads per chunk and wave the LDS pipe, not the matrix
+// pipe, then sets the pace.  LDS returns in order: after the reads of frequencies f+4, f+5 are issued, 8 newer
+// reads than those of f, f+1 are outstanding.
+__device__ __forceinline__ void wn_consume_chunk(f32x4 (&acc)[WN_FREQ], const f32x2* a_img, const f32x2* b_img, int ablate) {
+    const unsigned a_addr = (unsigned)(size_t)(__attribute__((address_space(3))) const void*)a_img;
+    const unsigned b_addr = (unsigned)(size_t)(__attribute__((address_space(3))) const void*)b_img;
+    f32x2 fa[WN_FREQ], fb[WN_FREQ];
+#define WN_RD(f_)                                                                                                      \
+    asm volatile("ds_read_b64 %0, %2 offset:%4\n\tds_read_b64 %1, %3 offset:%4" : "=&v"(fa[f_]), "=&v"(fb[f_]) : "v"(a_addr), "v"(b_addr), "n"((f_) * 1024))
+#define WN_WAIT(f_, n_)                                                                                                \
+    asm volatile("s_waitcnt lgkmcnt(" #n_ ")" : "+v"(fa[f_]), "+v"(fb[f_]), "+v"(fa[(f_) + 1]), "+v"(fb[(f_) + 1]))
+    WN_RD(0);
+    WN_RD(1);
+    WN_RD(2);
+    WN_RD(3);
+#pragma unroll
+    for (int f = 0; f < WN_FREQ; f += 2) {
+        if (f + 4 < WN_FREQ) {
+            WN_RD(f + 4);
+            WN_RD(f + 5);
+            WN_WAIT(f, 8);
+        } else if (f + 2 < WN_FREQ) {
+            WN_WAIT(f, 4);
+        } else {
+            WN_WAIT(f, 0);
+        }
+        if (ablate & 8) continue;
+        acc[f] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[f][0], fb[f][0], acc[f], 0, 0, 0);
+        acc[f + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[f + 1][0], fb[f + 1][0], acc[f + 1], 0, 0, 0);
+        acc[f] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[f][1], fb[f][1], acc[f], 0, 0, 0);
+        acc[f + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[f + 1][1], fb[f + 1][1], acc[f + 1], 0, 0, 0);
+    }
+#undef WN_RD
+#undef WN_WAIT
+}
 
-// Output transform of one wave's 16 tiles x 16 channels with the three endings of a stream-K segment:
-//   slab_out != null            contributor: partial sums -> slab (no bias), then publish
-//   else                        add the n_in contributor slabs slab_in + k * stride (k = 0 .. n_in - 1, in order), bias, store y
-// Slab element of (lane n, quad q, register r, row i): ((n * 4 + i) * 4 + r) * 16 + q * 4 .. +3 inside the wave's quarter:
-// the four quads of a store instruction write 64 contiguous bytes.
-__device__ __forceinline__ void ws_epilogue(const f32x4 (&acc)[WN_FREQ], float* __restrict__ y, const float* __restrict__ bias,
-                                            int tile_base, int co, const WinoGeom& g, int lane, float* __restrict__ slab_out,
-                                            const float* __restrict__ slab_in, int n_in, size_t slab_stride) {
-    const float bv = (bias && !slab_out) ? bias[co] : 0.0f;
-    const bool vec4 = (g.W & 3) == 0;
-    const int n = lane & 15, q = lane >> 4;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int tile = tile_base + 4 * r + q;
-        float tmp[4][6];
-#pragma unroll
-        for (int j = 0; j < 6; ++j)
-            wn_at(acc[0 * 6 + j][r], acc[1 * 6 + j][r], acc[2 * 6 + j][r], acc[3 * 6 + j][r], acc[4 * 6 + j][r], acc[5 * 6 + j][r],
-                  tmp[0][j], tmp[1][j], tmp[2][j], tmp[3][j]);
-        f32x4 o[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            float o0, o1, o2, o3;
-            wn_at(tmp[i][0], tmp[i][1], tmp[i][2], tmp[i][3], tmp[i][4], tmp[i][5], o0, o1, o2, o3);
-            o[i] = f32x4{o0, o1, o2, o3};
-        }
-        if (slab_out) {
-            // write-through (sc1) stores: the bytes leave this XCD's L2 without an L2-wide release fence (a buffer_wbl2 per
-            // publishing wave wrote back every dirty line of the XCD - the other workgroups' output rows included)
-            const __amdgpu_buffer_rsrc_t sr = wn_rsrc(slab_out, (unsigned)(WS_SLAB_FLOATS / 4) * 4u);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4w, o[i]), sr, (unsigned)(((n * 4 + i) * 4 + r) * 16 + q * 4) * 4u, 0, 16);
-            continue;
-        }
-        for (int k = 0; k < n_in; ++k) {
-            const float* sl = slab_in + (size_t)k * slab_stride;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) o[i] += *reinterpret_cast<const f32x4*>(sl + ((n * 4 + i) * 4 + r) * 16 + q * 4);
-        }
-        if (tile >= g.n_tiles) continue;
-        const int b = tile / g.tiles_img, rem = tile - b * g.tiles_img;
-        const int ty = rem / g.tiles_x, tx = rem - ty * g.tiles_x;
-        float* const row0 = y + (((size_t)b * g.Cout + co) * g.H + 4 * ty) * g.W + 4 * tx;
-        const bool right = 4 * tx + 3 < g.W;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (4 * ty + i < g.H) {
-                float* p = row0 + (size_t)i * g.W;
-                const f32x4 v = o[i] + f32x4{bv, bv, bv, bv};
-                if (vec4) {
-                    *reinterpret_cast<f32x4*>(p) = v;
-                } else {
-                    *reinterpret_cast<f32x2*>(p) = f32x2{v[0], v[1]};
-                    if (right) *reinterpret_cast<f32x2*>(p + 2) = f32x2{v[2], v[3]};
-                }
-            }
-        }
+// The producers' pipeline over the `total` chunks of a workgroup: two register stages, each FETCHED two chunks ahead and only
+// touched when its chunk is PRODUCED into the LDS images (q & 1); a producer's barrier is "my LDS writes are done" (lgkmcnt) - it
+// never waits for loads in flight.  fetch(stage, q) always issues the same loads, past the end of the range against an empty
+// descriptor (hardware zeros, no memory access): the compiler's vmcnt bookkeeping is then the same on every path, and a wait for the
+// previous period's registers never has to cover "or the fetch was skipped" by draining the loads just issued.
+template <class Stage, class Fetch, class Produce>
+__device__ __forceinline__ void wn_produce_stream(int total, Fetch fetch, Produce produce) {
+    auto barrier = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
+    Stage s0, s1;
+    fetch(s0, 0);
+    fetch(s1, 1);
+    produce(s0, 0);                 // chunk 0 -> images 0
+    // loop body unrolled by two so that the stage registers alternate without copies
+    int q = 0;
+    while (true) {
+        barrier();                  // barrier q: images of chunk q published
+        if (q + 1 >= total) break;
+        fetch(s0, q + 2);
+        produce(s1, (q + 1) & 1);
+        ++q;
+        barrier();                  // barrier q
+        if (q + 1 >= total) break;
+        fetch(s1, q + 2);
+        produce(s0, (q + 1) & 1);
+        ++q;
     }
 }
 
@@ -575,8 +628,7 @@ wino_fwd_ws_kernel(const float* __restrict__ x, const float* __restrict__ u, con
     const int n_groups = gang ? g.n_cout_blocks / gsz : 1;
     const long long S = (long long)(gang ? n_groups * g.n_tile_blocks : n_units) * g.n_chunks;
     const long long lo = ws_range_lo(rng, G, S), hi = ws_range_lo(rng + 1, G, S);
-    // (64-bit division runs on the vector ALU: hand the wave-uniform results back to scalar registers, or every use as a
-    // scalar operand - the loads' soffset - becomes a waterfall loop)
+    // (wave-uniform, to scalar registers: see ws_cursor)
     const int total = __builtin_amdgcn_readfirstlane((int)(hi - lo));   // chunks this workgroup multiplies = barriers every wave passes
     if (total == 0) return;
     auto tb_of = [&](int useq) { return gang ? useq % g.n_tile_blocks : useq / g.n_cout_blocks; };
@@ -590,51 +642,15 @@ wino_fwd_ws_kernel(const float* __restrict__ x, const float* __restrict__ u, con
         int q = 0;
         long long s = lo;
         while (s < hi) {
-            const int unit = (int)(s / g.n_chunks);
-            const int c_begin = (int)(s - (long long)unit * g.n_chunks);
-            const int c_end = (hi - s < g.n_chunks - c_begin) ? c_begin + (int)(hi - s) : g.n_chunks;
+            const WinoCursor at = ws_cursor(s, g.n_chunks);
+            const int unit = at.unit, c_begin = at.chunk, c_end = ws_segment_end(s, hi, c_begin, g.n_chunks);
             const int tb = tb_of(unit), cb = cb_of(unit);
             f32x4 acc[WN_FREQ];
 #pragma unroll
             for (int f = 0; f < WN_FREQ; ++f) acc[f] = f32x4{0.f, 0.f, 0.f, 0.f};
             for (int chunk = c_begin; chunk < c_end; ++chunk, ++q) {
                 __syncthreads();                                  // images of chunk q complete, images of q - 1 free
-                // Fragment reads as inline-asm ds_read_b64 with a counted lgkmcnt: left to itself hipcc fuses the 8-byte reads of
-                // two frequencies into ds_read2st64_b64, which moves the same bytes at HALF the LDS rate (128 instead of 256
-                // B/clk, MI355X_MICROARCH.md LDS table) - with 72 fragment reads per chunk and wave the LDS pipe, not the matrix
-                // pipe, then sets the pace.  LDS returns in order: after the reads of frequencies f+4, f+5 are issued, 8 newer
-                // reads than those of f, f+1 are outstanding.
-                if (ablate & 8) continue;
-                const unsigned a_addr = (unsigned)(size_t)(__attribute__((address_space(3))) const void*)(a_frag + (q & 1) * (IMG / 2));
-                const unsigned b_addr = (unsigned)(size_t)(__attribute__((address_space(3))) const void*)(b_frag + (q & 1) * (IMG / 2));
-                f32x2 fa[WN_FREQ], fb[WN_FREQ];
-#define WN_RD(f_)                                                                                                      \
-    asm volatile("ds_read_b64 %0, %2 offset:%4\n\tds_read_b64 %1, %3 offset:%4" : "=&v"(fa[f_]), "=&v"(fb[f_]) : "v"(a_addr), "v"(b_addr), "n"((f_) * 1024))
-#define WN_WAIT(f_, n_)                                                                                                \
-    asm volatile("s_waitcnt lgkmcnt(" #n_ ")" : "+v"(fa[f_]), "+v"(fb[f_]), "+v"(fa[(f_) + 1]), "+v"(fb[(f_) + 1]))
-                WN_RD(0);
-                WN_RD(1);
-                WN_RD(2);
-                WN_RD(3);
-#pragma unroll
-                for (int f = 0; f < WN_FREQ; f += 2) {
-                    if (f + 4 < WN_FREQ) {
-                        WN_RD(f + 4);
-                        WN_RD(f + 5);
-                        WN_WAIT(f, 8);
-                    } else if (f + 2 < WN_FREQ) {
-                        WN_WAIT(f, 4);
-                    } else {
-                        WN_WAIT(f, 0);
-                    }
-                    if (ablate & 8) continue;
-                    acc[f] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[f][0], fb[f][0], acc[f], 0, 0, 0);
-                    acc[f + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[f + 1][0], fb[f + 1][0], acc[f + 1], 0, 0, 0);
-                    acc[f] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[f][1], fb[f][1], acc[f], 0, 0, 0);
-                    acc[f + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[f + 1][1], fb[f + 1][1], acc[f + 1], 0, 0, 0);
-                }
-#undef WN_RD
-#undef WN_WAIT
+                wn_consume_chunk(acc, a_frag + (q & 1) * (IMG / 2), b_frag + (q & 1) * (IMG / 2), ablate);
             }
             s += c_end - c_begin;
             const int tile_base = tb * WN_TILES + wt * 16, co = cb * WN_COUT + wc * 16 + (lane & 15);
@@ -677,7 +693,6 @@ wino_fwd_ws_kernel(const float* __restrict__ x, const float* __restrict__ u, con
                     if (lane == 0)
                         for (int k2 = 1; k2 <= n_in; ++k2) __hip_atomic_store(flags + (w + k2 * gsz) * 4 + wave, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
-
             }
         }
     } else {
@@ -691,10 +706,8 @@ wino_fwd_ws_kernel(const float* __restrict__ x, const float* __restrict__ u, con
             const int tb = tb_of(unit);
             return wn_patch_off(tb * WN_TILES + t_grp * 16 + t_t, t_t, t_c, g.Cin, g);
         };
-        // Everything a chunk needs from global memory (its 6x6 patch and the thread's 9 x 16 bytes of the transformed filters)
-        // is LOADED TWO CHUNKS AHEAD into registers and only touched when the chunk is produced; the barrier of a producer is
-        // "my LDS writes are done" (lgkmcnt) - it never waits for loads in flight.  Measured (128 -> 128 @ 188^2, 105 us): this
-        // removes the forced waits the ISA showed (a patch post-processed at issue, a vmcnt(0) in front of every barrier) but not
+        // A stage of wn_produce_stream: everything a chunk needs from global memory (its 6x6 patch and the thread's 9 x 16 bytes of
+        // the transformed filters).  Measured (128 -> 128 @ 188^2, 105 us): loading two chunks ahead removes the forced waits the ISA showed (a patch post-processed at issue, a vmcnt(0) in front of every barrier) but not
         // the time - the loads cost ~10 us each (patches, filters) whether they get one period of cover or two, i.e. memory-path
         // throughput, not latency; the filters by LDS-DMA issued first in the period measure the same.  What does not overlap
         // at all is the transform's vector-ALU work: fp32 MFMA and packed fp32 VALU share one datapath on this part (equal
@@ -727,17 +740,13 @@ wino_fwd_ws_kernel(const float* __restrict__ x, const float* __restrict__ u, con
         };
 
         // chunk stream of this workgroup: step lo + q -> (unit, chunk); units are consecutive
-        const int unit0 = __builtin_amdgcn_readfirstlane((int)(lo / g.n_chunks));
-        const int chunk0 = __builtin_amdgcn_readfirstlane((int)(lo - (long long)unit0 * g.n_chunks));
-        WinoCursor ld{unit0, chunk0};       // next chunk to fetch
-        PatchOff pa = patch_of(unit0);
+        WinoCursor ld = ws_cursor(lo, g.n_chunks, true);       // next chunk to fetch
+        PatchOff pa = patch_of(ld.unit);
         const unsigned x_bytes = (unsigned)((size_t)g.B * g.Cin * g.H * g.W * 4u), u_bytes = (unsigned)((size_t)WN_FREQ * g.Cin * g.Cout * 4u);
         const unsigned u_voff = (unsigned)pt * 16u;
         auto fetch = [&](Stage& st, int q_fetch) {
-            // ALWAYS the same 21 loads, past the end of the range against an empty descriptor (hardware zeros, no memory access):
-            // the compiler's vmcnt bookkeeping is then the same on every path, and a wait for the previous period's registers
-            // never has to cover "or the fetch was skipped" by draining the loads just issued.  No vector-ALU work between the
-            // loads: per-thread offsets are fixed registers, the chunk moves the scalar offset.
+            // always the same 21 loads (see wn_produce_stream).  No vector-ALU work between the loads: per-thread offsets are fixed
+            // registers, the chunk moves the scalar offset.
             const bool live = q_fetch < total;
             const __amdgpu_buffer_rsrc_t xr_q = wn_rsrc(x, live && !(ablate & 1) ? x_bytes : 0u);
             const __amdgpu_buffer_rsrc_t ur_q = wn_rsrc(u, live && !(ablate & 2) ? u_bytes : 0u);
@@ -754,38 +763,20 @@ wino_fwd_ws_kernel(const float* __restrict__ x, const float* __restrict__ u, con
                 }
             }
         };
-        auto barrier = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
-        Stage s0, s1;
-        fetch(s0, 0);
-        fetch(s1, 1);
-        produce(s0, 0);                 // chunk 0 -> images 0
-        // loop body unrolled by two so that the stage registers alternate without copies
-        int q = 0;
-        while (true) {
-            barrier();                  // barrier q
-            if (q + 1 >= total) break;
-            fetch(s0, q + 2);
-            produce(s1, (q + 1) & 1);
-            ++q;
-            barrier();                  // barrier q
-            if (q + 1 >= total) break;
-            fetch(s1, q + 2);
-            produce(s0, (q + 1) & 1);
-            ++q;
-        }
+        wn_produce_stream<Stage>(total, fetch, produce);
     }
 }
 
 // ------------------------------------------------------------------------------------------------------------------
 // Weight gradient in the Winograd domain: dU[f][ci][co] = sum over tiles V[f][tile][ci] * dM[f][tile][co],
 // V = B^T x B (the forward's input transform), dM = A dY A^T (the transpose of the output transform), then
-// dw[co][ci] = G^T dU G.  Same machine as the forward kernel - the contraction index is the TILE instead of the input
-// channel: a chunk is 8 consecutive tiles, the A image holds V (rows = 32 input channels), the B image dM (columns = 32 output
+// dw[co][ci] = G^T dU G.  The machine of wino_fwd_ws_kernel (ws_cursor, wn_consume_chunk, wn_produce_stream) - the contraction
+// index is the TILE instead of the input channel: a chunk is 8 consecutive tiles, the A image holds V (rows = 32 input channels), the B image dM (columns = 32 output
 // channels), 36 frequencies x 2 MFMA k-steps per chunk and consumer wave.  Producers: waves 4-5 transform x (one thread =
 // one channel x two neighbouring tiles: both patches of an image row from two 16-byte loads and two halo loads), waves 6-7
 // transform dY; a thread's two tiles are the two k-slots of one 8-byte LDS store.
 // Stream-K over (unit = (ci block, co block), chunk): every segment's 36 x 32 x 32 partial sums go to slab (w + unit);
-// wino_wgrad_finish_kernel adds the slabs of a unit in workgroup order and applies G^T . G.  No float atomics.
+// wino_wgrad_fold_kernel adds the slabs of a unit in workgroup order and applies G^T . G.  No float atomics.
 // ------------------------------------------------------------------------------------------------------------------
 constexpr int WG_KT = 8;                                  // tiles per chunk
 constexpr int WG_SLAB_FLOATS = WN_FREQ * 32 * 32;         // [f][co 32][ci 32]
@@ -948,46 +939,14 @@ wino_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ dy, con
         int q = 0;
         long long s = lo;
         while (s < hi) {
-            const int unit = (int)(s / wg.steps_per_unit);
-            const int c_begin = (int)(s - (long long)unit * wg.steps_per_unit);
-            const int c_end = (hi - s < wg.steps_per_unit - c_begin) ? c_begin + (int)(hi - s) : wg.steps_per_unit;
+            const WinoCursor at = ws_cursor(s, wg.steps_per_unit);
+            const int unit = at.unit, c_begin = at.chunk, c_end = ws_segment_end(s, hi, c_begin, wg.steps_per_unit);
             f32x4 acc[WN_FREQ];
 #pragma unroll
             for (int f = 0; f < WN_FREQ; ++f) acc[f] = f32x4{0.f, 0.f, 0.f, 0.f};
             for (int chunk = c_begin; chunk < c_end; ++chunk, ++q) {
                 __syncthreads();
-                // fragment reads as single ds_read_b64 with a counted lgkmcnt, as in wino_fwd_ws_kernel (left alone hipcc pairs
-                // them into ds_read2st64_b64: the same bytes at half the LDS rate)
-                const unsigned a_addr = (unsigned)(size_t)(__attribute__((address_space(3))) const void*)(a_frag + (q & 1) * (IMG / 2));
-                const unsigned b_addr = (unsigned)(size_t)(__attribute__((address_space(3))) const void*)(b_frag + (q & 1) * (IMG / 2));
-                f32x2 fa[WN_FREQ], fb[WN_FREQ];
-#define WN_RD(f_)                                                                                                      \
-    asm volatile("ds_read_b64 %0, %2 offset:%4\n\tds_read_b64 %1, %3 offset:%4" : "=&v"(fa[f_]), "=&v"(fb[f_]) : "v"(a_addr), "v"(b_addr), "n"((f_) * 1024))
-#define WN_WAIT(f_, n_)                                                                                                \
-    asm volatile("s_waitcnt lgkmcnt(" #n_ ")" : "+v"(fa[f_]), "+v"(fb[f_]), "+v"(fa[(f_) + 1]), "+v"(fb[(f_) + 1]))
-                WN_RD(0);
-                WN_RD(1);
-                WN_RD(2);
-                WN_RD(3);
-#pragma unroll
-                for (int f = 0; f < WN_FREQ; f += 2) {
-                    if (f + 4 < WN_FREQ) {
-                        WN_RD(f + 4);
-                        WN_RD(f + 5);
-                        WN_WAIT(f, 8);
-                    } else if (f + 2 < WN_FREQ) {
-                        WN_WAIT(f, 4);
-                    } else {
-                        WN_WAIT(f, 0);
-                    }
-                    if (ablate & 8) continue;
-                    acc[f] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[f][0], fb[f][0], acc[f], 0, 0, 0);
-                    acc[f + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[f + 1][0], fb[f + 1][0], acc[f + 1], 0, 0, 0);
-                    acc[f] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[f][1], fb[f][1], acc[f], 0, 0, 0);
-                    acc[f + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[f + 1][1], fb[f + 1][1], acc[f + 1], 0, 0, 0);
-                }
-#undef WN_RD
-#undef WN_WAIT
+                wn_consume_chunk(acc, a_frag + (q & 1) * (IMG / 2), b_frag + (q & 1) * (IMG / 2), ablate);
             }
             s += c_end - c_begin;
             // segment done: acc[f][r] = dU[f][ci = 16 wm + 4 quad + r][co = 16 wn + (lane & 15)] -> slab [f][co][ci]
@@ -1000,15 +959,12 @@ wino_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ dy, con
         const int pw = wave - 4;
         const int k = (lane & 3) + 4 * (pw & 1), slot = (lane >> 2) + 16 * (pw >> 1);
         const int img_off = (slot >> 4) * 128 + ((k >> 1) * 16 + (slot & 15)) * 2 + (k & 1);
-        int unit = __builtin_amdgcn_readfirstlane((int)(lo / wg.steps_per_unit));
-        int chunk = __builtin_amdgcn_readfirstlane((int)(lo - (long long)unit * wg.steps_per_unit));
+        const WinoCursor first = ws_cursor(lo, wg.steps_per_unit, true);
+        int unit = first.unit, chunk = first.chunk;       // next chunk to fetch
         TilePos tp = wn_tile_pos(chunk * WG_KT + k, g);
         const unsigned x_bytes = (unsigned)((size_t)g.B * g.Cin * g.H * g.W * 4u), y_bytes = (unsigned)((size_t)g.B * g.Cout * g.H * g.W * 4u);
 
-        // Two register stages, loaded two chunks ahead and untouched until their chunk is produced; always the same loads (an
-        // empty descriptor past the end of the range: hardware zeros, no memory access) so that the compiler's vmcnt waits are the
-        // same on every path; the producers' barrier waits for their LDS writes only (see wino_fwd_ws_kernel).
-        struct WStage {
+        struct WStage {                     // see wn_produce_stream
             XRaw x;
             DyRaw y;
         };
@@ -1042,24 +998,7 @@ wino_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ dy, con
             wn_x_transform_store(st.x, lds + buf * IMG + img_off);
             wn_dy_transform_store(st.y, lds + (2 + buf) * IMG + img_off);
         };
-        auto barrier = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
-        WStage s0, s1;
-        fetch(s0, 0);
-        fetch(s1, 1);
-        produce(s0, 0);
-        int q = 0;
-        while (true) {
-            barrier();                  // barrier q: images of chunk q published
-            if (q + 1 >= total) break;
-            fetch(s0, q + 2);
-            produce(s1, (q + 1) & 1);
-            ++q;
-            barrier();
-            if (q + 1 >= total) break;
-            fetch(s1, q + 2);
-            produce(s0, (q + 1) & 1);
-            ++q;
-        }
+        wn_produce_stream<WStage>(total, fetch, produce);
     }
 }
 
@@ -1078,6 +1017,31 @@ __device__ __forceinline__ int wn_unit_segments(int unit, int n_units, int steps
         lo = next;
     }
     return n;
+}
+
+// The fixed-order fold of a unit's segment slabs, N sums per thread: acc[k] (zero on entry) += p[k][seg[i] * stride], i = 0 .. n - 1, added in segment
+// (= workgroup) order - that order is the contract between the two fold routes - with the loads of eight segments in flight together.
+template <int N>
+__device__ __forceinline__ void wn_fold_segments(const float* const (&p)[N], const int* seg, int n, size_t stride, float (&acc)[N]) {
+    int i = 0;
+    for (; i + 8 <= n; i += 8) {
+        float v[N][8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const size_t off = (size_t)seg[i + j] * stride;
+#pragma unroll
+            for (int k = 0; k < N; ++k) v[k][j] = p[k][off];
+        }
+#pragma unroll
+        for (int k = 0; k < N; ++k)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc[k] += v[k][j];
+    }
+    for (; i < n; ++i) {
+        const size_t off = (size_t)seg[i] * stride;
+#pragma unroll
+        for (int k = 0; k < N; ++k) acc[k] += p[k][off];
+    }
 }
 
 // dw[3][3] of one (co, ci) = G^T dU G in fp64 from its 36 folded sums
@@ -1104,8 +1068,8 @@ __device__ __forceinline__ void wn_filter_grad(const double (&du)[WN_FREQ], floa
 }
 
 // Fold and G^T . G in one kernel (the default): a workgroup owns one co row of a unit = 32 (co, ci) pairs, 128 consecutive bytes of
-// every frequency plane of a slab.  Its 256 threads split the 36 x 32 sums (4.5 each, the loads of eight segments of all of a
-// thread's sums in flight together, added in workgroup order as in wino_wgrad_reduce_kernel: the same bits), hand them over
+// every frequency plane of a slab.  Its 256 threads split the 36 x 32 sums (4.5 each, all of a thread's sums in one
+// wn_fold_segments: the bits of wino_wgrad_reduce_kernel), hand them over
 // through LDS, and the 32 pair threads apply G^T dU G.  32 workgroups per unit keep as many loads in flight over the slabs as the
 // one-thread-per-element fold did, and the per-unit sums never travel to HBM and back.
 constexpr int WF_PAIRS = 32;                                        // pairs per workgroup
@@ -1131,25 +1095,7 @@ wino_wgrad_fold_kernel(const float* __restrict__ slabs, const WgradGeom wg, int 
         p[k] = slabs + (size_t)unit * WG_SLAB_FLOATS + (idx >> 5) * 1024 + row * 32 + (idx & 31);
         acc[k] = 0.0f;
     }
-    int i = 0;
-    for (; i + 8 <= n; i += 8) {
-        float v[WF_SUMS][8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const size_t off = (size_t)seg[i + j] * WG_SLAB_FLOATS;
-#pragma unroll
-            for (int k = 0; k < WF_SUMS; ++k) v[k][j] = p[k][off];
-        }
-#pragma unroll
-        for (int k = 0; k < WF_SUMS; ++k)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc[k] += v[k][j];
-    }
-    for (; i < n; ++i) {
-        const size_t off = (size_t)seg[i] * WG_SLAB_FLOATS;
-#pragma unroll
-        for (int k = 0; k < WF_SUMS; ++k) acc[k] += p[k][off];
-    }
+    wn_fold_segments(p, seg, n, WG_SLAB_FLOATS, acc);
 #pragma unroll
     for (int k = 0; k < WF_SUMS; ++k)
         if (tid + k * WN_BLOCK < WN_FREQ * WF_PAIRS) du_s[tid + k * WN_BLOCK] = acc[k];
@@ -1172,7 +1118,7 @@ __global__ void __launch_bounds__(WN_BLOCK)
 wino_wgrad_reduce_kernel(const float* __restrict__ slabs, const int n_units, const int steps_per_unit, int G, float* __restrict__ red) {
     // SLAB is a multiple of the block size: a block lies inside one unit, whose segment list (which workgroups of the
     // stream-K split touched it) thread 0 works out once - the 64-bit divisions of ws_range_lo per thread and per segment cost more
-    // than the fold itself; the loads of eight segments are then in flight together, the adds stay in workgroup order
+    // than the fold itself
     static_assert(SLAB % WN_BLOCK == 0, "a fold block must not straddle two units");
     __shared__ int seg[WS_MAX_GRID];
     __shared__ int n_seg;
@@ -1182,19 +1128,10 @@ wino_wgrad_reduce_kernel(const float* __restrict__ slabs, const int n_units, con
     __syncthreads();
     if (unit >= n_units) return;
     const int off = (int)(e - (long long)unit * SLAB);
-    const float* p = slabs + (size_t)unit * SLAB + off;
-    const int n = n_seg;
-    float acc = 0.0f;
-    int i = 0;
-    for (; i + 8 <= n; i += 8) {
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = p[(size_t)seg[i + j] * SLAB];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc += v[j];
-    }
-    for (; i < n; ++i) acc += p[(size_t)seg[i] * SLAB];
-    red[e] = acc;
+    const float* const p[1] = {slabs + (size_t)unit * SLAB + off};
+    float acc[1] = {0.0f};
+    wn_fold_segments(p, seg, n_seg, SLAB, acc);
+    red[e] = acc[0];
 }
 
 // stage 2: dw[co][ci][3][3] = G^T dU G
@@ -1212,7 +1149,6 @@ wino_wgrad_finish_kernel(const float* __restrict__ red, const WgradGeom wg, floa
     wn_filter_grad(du, dw + ((size_t)co * cin + ci) * 9);
 }
 
-
 static int wino_geom(const char* who, int batch, int cin, int cout, int H, int W, WinoGeom* g) {
     TODA_CHECK_ARG(batch >= 1 && H >= 1 && W >= 2 && W % 2 == 0, "%s: needs batch >= 1, H >= 1 and an even W (got %d x %d x %d)", who, batch, H, W);
     TODA_CHECK_ARG(cin >= WN_KC && cin % WN_KC == 0, "%s: input channels must be a multiple of %d (got %d)", who, WN_KC, cin);
@@ -1227,6 +1163,37 @@ static int wino_geom(const char* who, int batch, int cin, int cout, int H, int W
     g->n_cout_blocks = cout / WN_COUT;
     g->n_chunks = cin / WN_KC;
     return TODA_OK;
+}
+
+// Gang size of a wino_fwd_ws_kernel launch on n_cu workgroups, 0 = no gangs (see the kernel; tests/conv2d_routes.py::wino_gang is the
+// mirror): the largest power-of-two divisor of the channel-block count whose filters (size x 36 x Cin x 32 floats) fit TODA_WINO_GANG_KB
+// (2560 KiB of the XCD's 4 MiB L2); TODA_WINO_GANG = 0: no gangs, 1: this rule, -1: round 3's gang of all blocks
+static int wino_gang(const WinoGeom& g, int n_cu) {
+    static const int env_gang = getenv("TODA_WINO_GANG") ? atoi(getenv("TODA_WINO_GANG")) : 1;
+    static const int gang_kb = getenv("TODA_WINO_GANG_KB") ? atoi(getenv("TODA_WINO_GANG_KB")) : 2560;
+    const int ncb = g.n_cout_blocks;
+    if (!(env_gang && ncb > 1 && ncb <= 32 && (32 % ncb) == 0 && (n_cu % ncb) == 0)) return 0;
+    int gang = ncb;
+    const long long slice = (long long)WN_FREQ * g.Cin * WN_COUT * 4;
+    while (env_gang > 0 && gang > 1 && gang * slice > (long long)gang_kb * 1024) gang >>= 1;
+    return (long long)(ncb / gang) * g.n_tile_blocks * g.n_chunks < n_cu / gang ? 0 : gang;
+}
+
+// One filter-transform entry: pointers, mode, channel multiples and the 2^31 bound; *threads = threads of its launch
+static int wino_weight_check(const char* who, const float* w, const float* u, int cout, int cin, int mode, long long* threads) {
+    TODA_CHECK_ARG(w && u && mode >= 0 && mode <= 2, "%s: null pointer or bad mode", who);
+    const int CO = mode == 1 ? cin : cout, CI = mode == 1 ? cout : cin;
+    TODA_CHECK_ARG(CO % WN_COUT == 0 && CI % WN_KC == 0 && CO > 0 && CI > 0 && (mode != 2 || (CI % WN_COUT == 0)),
+                   "%s: produced channels %% 32 and contracted channels %% 8 must be 0 (got %d, %d)", who, CO, CI);
+    *threads = 6LL * cout * cin * (mode == 2 ? 2 : 1);
+    TODA_CHECK_ARG(*threads * 6 < (1LL << 31), "%s: operand above 2^31 elements", who);
+    return TODA_OK;
+}
+
+static int wino_workspace_check(const char* who, const void* ws, size_t ws_bytes, size_t need) {
+    if (ws && ws_bytes >= need) return TODA_OK;
+    toda::set_error("%s: workspace too small (%zu < %zu bytes)", who, ws_bytes, need);
+    return TODA_EWORKSPACE;
 }
 
 }  // namespace toda
@@ -1245,12 +1212,8 @@ extern "C" int toda_conv3x3_supported(int batch, int cin, int cout, int H, int W
 }
 
 extern "C" int toda_conv3x3_transform_weight(const float* w, int cout, int cin, int mode, float* u, void* stream) {
-    TODA_CHECK_ARG(w && u && mode >= 0 && mode <= 2, "conv3x3_transform_weight: null pointer or bad mode");
-    const int CO = mode == 1 ? cin : cout, CI = mode == 1 ? cout : cin;
-    TODA_CHECK_ARG(CO % WN_COUT == 0 && CI % WN_KC == 0 && CO > 0 && CI > 0 && (mode != 2 || (CI % WN_COUT == 0)),
-                   "conv3x3_transform_weight: produced channels %% 32 and contracted channels %% 8 must be 0 (got %d, %d)", CO, CI);
-    const long long threads = 6LL * cout * cin * (mode == 2 ? 2 : 1);
-    TODA_CHECK_ARG(threads * 6 < (1LL << 31), "conv3x3_transform_weight: operand above 2^31 elements");
+    long long threads;
+    if (const int rc = wino_weight_check("conv3x3_transform_weight", w, u, cout, cin, mode, &threads)) return rc;
     hipLaunchKernelGGL(wino_weight_kernel, dim3(cdiv(threads, WN_BLOCK)), dim3(WN_BLOCK), 0, (hipStream_t)stream, w, cout, cin, mode, u);
     TODA_LAUNCH_CHECK();
     return TODA_OK;
@@ -1270,12 +1233,10 @@ extern "C" int toda_conv3x3_transform_weight_batch(const toda_conv3x3_weight_ent
     for (int i = 0; i < n; ++i) {
         const toda_conv3x3_weight_entry& t = table[i];
         const int cout = t.cout, cin = t.cin, mode = t.mode;
-        TODA_CHECK_ARG(t.w && t.u && mode >= 0 && mode <= 2, "conv3x3_transform_weight_batch: entry %d: null pointer or bad mode", i);
-        const int CO = mode == 1 ? cin : cout, CI = mode == 1 ? cout : cin;
-        TODA_CHECK_ARG(CO % WN_COUT == 0 && CI % WN_KC == 0 && CO > 0 && CI > 0 && (mode != 2 || (CI % WN_COUT == 0)),
-                       "conv3x3_transform_weight_batch: entry %d: produced channels %% 32 and contracted channels %% 8 must be 0 (got %d, %d)", i, CO, CI);
-        const long long threads = 6LL * cout * cin * (mode == 2 ? 2 : 1);
-        TODA_CHECK_ARG(threads * 6 < (1LL << 31), "conv3x3_transform_weight_batch: entry %d: operand above 2^31 elements", i);
+        char who[64];
+        snprintf(who, sizeof(who), "conv3x3_transform_weight_batch: entry %d", i);
+        long long threads;
+        if (const int rc = wino_weight_check(who, t.w, t.u, cout, cin, mode, &threads)) return rc;
         const long long blocks = cdiv(threads, WN_BLOCK);
         if (b.n == WB_MAX_LAYERS || (b.n > 0 && b.first_block[b.n] + blocks >= (1LL << 31))) {
             const int rc = flush();
@@ -1306,33 +1267,12 @@ extern "C" int toda_conv3x3_fwd(const float* x, const float* u, const float* bia
         hipLaunchKernelGGL(wino_fwd_kernel, dim3(n_units), dim3(WN_BLOCK), 0, (hipStream_t)stream, x, u, bias, y, g);
     } else {
         TODA_CHECK_ARG(ws != nullptr, "conv3x3_fwd: workspace missing");
-        if (ws_bytes < toda_conv3x3_workspace_bytes()) {
-            toda::set_error("conv3x3_fwd: workspace too small (%zu < %zu bytes)", ws_bytes, toda_conv3x3_workspace_bytes());
-            return TODA_EWORKSPACE;
-        }
-        static int n_cu = 0;
-        if (!n_cu) {
-            int dev = 0;
-            hipDeviceProp_t prop;
-            TODA_HIP(hipGetDevice(&dev));
-            TODA_HIP(hipGetDeviceProperties(&prop, dev));
-            n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-            if (n_cu > WS_MAX_GRID) n_cu = WS_MAX_GRID;
-        }
-        // one 144-KiB workgroup per CU; never more workgroups than chunk steps
-        // gang mode: n_cout_blocks workgroups per range of the (tile block, chunk) sequence (see the kernel)
-        // gang size: the largest power-of-two divisor of the channel-block count whose filters (size x 36 x Cin x 32 floats) fit
-        // TODA_WINO_GANG_KB (2560 KiB of the XCD's 4 MiB L2); TODA_WINO_GANG = 0: no gangs, 1: this rule, -1: round 3's gang of all blocks
-        static const int env_gang = getenv("TODA_WINO_GANG") ? atoi(getenv("TODA_WINO_GANG")) : 1;
-        static const int gang_kb = getenv("TODA_WINO_GANG_KB") ? atoi(getenv("TODA_WINO_GANG_KB")) : 2560;
-        const int ncb = g.n_cout_blocks;
-        int gang = 0;
-        if (env_gang && ncb > 1 && ncb <= 32 && (32 % ncb) == 0 && (n_cu % ncb) == 0) {
-            gang = ncb;
-            const long long slice = (long long)WN_FREQ * cin * WN_COUT * 4;
-            while (env_gang > 0 && gang > 1 && gang * slice > (long long)gang_kb * 1024) gang >>= 1;
-            if ((long long)(ncb / gang) * g.n_tile_blocks * g.n_chunks < n_cu / gang) gang = 0;
-        }
+        rc = wino_workspace_check("conv3x3_fwd", ws, ws_bytes, toda_conv3x3_workspace_bytes());
+        if (rc) return rc;
+        const int n_cu = std::min(cu_count(), WS_MAX_GRID);
+        // one 144-KiB workgroup per CU, never more workgroups than chunk steps; gang mode: the whole grid, `gang` workgroups per
+        // range of the sequence (see the kernel)
+        const int gang = wino_gang(g, n_cu);
         const long long steps = (long long)n_units * g.n_chunks;
         const int grid = gang ? n_cu : (steps < n_cu ? (int)steps : n_cu);
         int* flags = (int*)ws;                                  // 4 words per workgroup: zero on entry, zero again on exit
@@ -1365,7 +1305,6 @@ static int wgrad_geom(const char* who, int batch, int cin, int cout, int H, int 
     return TODA_OK;
 }
 
-
 extern "C" size_t toda_conv3x3_wgrad_workspace_bytes(int batch, int cin, int cout, int H, int W) {
     // one slab per stream-K segment (index w + unit) + the per-unit sums
     (void)batch, (void)H, (void)W;
@@ -1380,19 +1319,9 @@ extern "C" int toda_conv3x3_wgrad(const float* x, const float* dy, int batch, in
     int rc = wgrad_geom("conv3x3_wgrad", batch, cin, cout, H, W, &wg);
     if (rc) return rc;
     const size_t need = toda_conv3x3_wgrad_workspace_bytes(batch, cin, cout, H, W);
-    if (!ws || ws_bytes < need) {
-        toda::set_error("conv3x3_wgrad: workspace too small (%zu < %zu bytes)", ws_bytes, need);
-        return TODA_EWORKSPACE;
-    }
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        TODA_HIP(hipGetDevice(&dev));
-        TODA_HIP(hipGetDeviceProperties(&prop, dev));
-        n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        if (n_cu > WS_MAX_GRID) n_cu = WS_MAX_GRID;
-    }
+    rc = wino_workspace_check("conv3x3_wgrad", ws, ws_bytes, need);
+    if (rc) return rc;
+    const int n_cu = std::min(cu_count(), WS_MAX_GRID);
     const long long steps = (long long)wg.n_units * wg.steps_per_unit;
     const int grid = steps < n_cu ? (int)steps : n_cu;
     static const int ablate = (TODA_ABLATE && getenv("TODA_WINO_WG_ABLATE")) ? atoi(getenv("TODA_WINO_WG_ABLATE")) : 0;   // measurement builds only

@@ -429,15 +429,14 @@ static int fps_resident_blocks() {
         return 0;
     }
     if (dev < MAX_DEV && cached[dev] > 0) return cached[dev];
-    int cus = 0, per = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fps_multi_kernel, FPS_BLOCK, 0) != hipSuccess) {
+    int per = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fps_multi_kernel, FPS_BLOCK, 0) != hipSuccess) {
         (void)hipGetLastError();
         return 0;
     }
     per = per > 1 ? per - 1 : per;
     per = per > 4 ? 4 : per;
-    const int blocks = cus * per;
+    const int blocks = cu_count() * per;
     if (dev < MAX_DEV) cached[dev] = blocks;
     return blocks;
 }
