@@ -869,6 +869,40 @@ int toda_eval_match(const float* overlaps, const long long* ov_off, const int32_
                     int n_det_total, const double* thresholds, int n_thresh, double min_overlap, int metric, int compute_aos,
                     double* pr, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The device parts of the nuScenes detection metric (mAP / NDS, public definition `detection_cvpr_2019`; the reference hands
+ * the metric to the nuScenes devkit).  fp64 throughout, no atomics: two runs give the same bits.  Classes are numbered in
+ * the order car, truck, bus, trailer, construction_vehicle (range 50 m), pedestrian, motorcycle, bicycle (40 m),
+ * traffic_cone, barrier (30 m).
+ *
+ * toda_nusc_eval_prepare: n LiDAR-frame boxes, predictions or ground truths, to the global frame.  rows [n, 10] = x y z dx dy
+ * dz heading vx vy vz; sample [n] indexes G [n_samples, 12] (row-major 3 x 4, G = inv(car_from_global) . inv(ref_from_car))
+ * and ego [n_samples, 3] (the translation of inv(car_from_global)); cls [n] is the class number, anything outside 0..9 is
+ * never kept.  out [n, 6] = centre x y z, yaw, velocity x y; keep [n] = 1 iff the xy distance from the centre to ego is
+ * strictly below the class's range.  A row whose sample index lies outside [0, n_samples) gets NaN and keep 0.
+ *
+ * toda_nusc_eval_match: the greedy centre-distance matching of every (sample, class) segment at the four thresholds.
+ * pred / gt rows [., 8] = centre x y, yaw, velocity x y, dx dy dz, stored segment after segment; pred_off_host / gt_off_host
+ * (HOST, int32 [n_seg + 1]) are the CSR offsets of both sides and seg_cls_host (HOST, int32 [n_seg]) the class number of
+ * each segment; they are checked and copied into ws.  A segment holds at most TODA_NUSC_MAX_PRED predictions (the metric's
+ * own limit per sample) and TODA_NUSC_MAX_GT ground truths (64 lanes x the 32 bits of a lane's taken mask); more is refused.
+ * Predictions are visited by (score descending, position descending); each takes the nearest free ground truth of its segment
+ * (lowest position on equal distances) iff that distance is strictly below the threshold.  match [4, n_pred]: the row of the
+ * ground truth in gt, or -1.  err [5, n_pred], written for thresholds_host[tp_threshold] only: translation, velocity (NaN
+ * with a NaN ground-truth velocity), 1 - IoU of the centre-aligned sizes, yaw difference (period pi for barriers) and
+ * attribute (0 equal, 1 different, NaN when gt_attr < 0); NaN where unmatched.
+ * ws: toda_nusc_eval_match_workspace_bytes(n_seg) bytes.
+ * ---------------------------------------------------------------------- */
+#define TODA_NUSC_MAX_PRED 500
+#define TODA_NUSC_MAX_GT 2048
+int toda_nusc_eval_prepare(const double* rows, const int32_t* sample, const int32_t* cls, int n, const double* G,
+                           const double* ego, int n_samples, double* out, int32_t* keep, void* stream);
+size_t toda_nusc_eval_match_workspace_bytes(int n_seg);
+int toda_nusc_eval_match(const double* pred, const double* pred_score, const int32_t* pred_attr, int n_pred, const double* gt,
+                         const int32_t* gt_attr, int n_gt, const int32_t* pred_off_host, const int32_t* gt_off_host,
+                         const int32_t* seg_cls_host, int n_seg, const double* thresholds_host, int tp_threshold,
+                         int32_t* match, double* err, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -165,6 +165,9 @@ SIGNATURES = {
     "toda_eval_match_workspace_bytes": (_sz, [_i, _i, _i]),
     "toda_eval_match_scores": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _dbl, _vp, _vp, _vp, _sz, _vp]),
     "toda_eval_match": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _dbl, _i, _i, _vp, _vp, _sz, _vp]),
+    "toda_nusc_eval_prepare": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "toda_nusc_eval_match_workspace_bytes": (_sz, [_i]),
+    "toda_nusc_eval_match": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -1934,6 +1934,60 @@ def eval_match(overlaps, ov_off, det_off, gt_off, ign_det, ign_gt, score, det_al
     return pr
 
 
+NUSC_CLASSES = ("car", "truck", "bus", "trailer", "construction_vehicle", "pedestrian", "motorcycle", "bicycle", "traffic_cone", "barrier")
+NUSC_DIST_THS = (0.5, 1.0, 2.0, 4.0)
+NUSC_MAX_PRED, NUSC_MAX_GT = 500, 2048                  # TODA_NUSC_MAX_PRED / TODA_NUSC_MAX_GT of include/toda.h
+
+
+def nusc_eval_prepare(rows, sample, cls, G, ego):
+    """LiDAR-frame boxes of the nuScenes metric to the global frame (toda_nusc_eval_prepare).  rows fp64 [n, 10] = x y z dx dy dz
+    heading vx vy vz, sample / cls int32 [n] (cls indexes NUSC_CLASSES), G fp64 [S, 3, 4], ego fp64 [S, 3] ->
+    (out fp64 [n, 6] = centre x y z, yaw, velocity x y; keep int32 [n] = ego distance < the class's range)."""
+    rows, G, ego = (_eval_arg(t, torch.float64, "nusc_eval_prepare: rows, G and ego") for t in (rows, G, ego))
+    sample, cls = (_eval_arg(t, torch.int32, "nusc_eval_prepare: sample and cls") for t in (sample, cls))
+    n, n_samples = int(rows.shape[0]), int(G.shape[0])
+    if rows.dim() != 2 or rows.shape[1] != 10 or sample.numel() != n or cls.numel() != n:
+        raise RuntimeError("nusc_eval_prepare: rows must be [n, 10] with one sample index and one class per row")
+    if G.numel() != n_samples * 12 or ego.numel() != n_samples * 3:
+        raise RuntimeError("nusc_eval_prepare: G must be [S, 3, 4] and ego [S, 3]")
+    out = torch.empty((n, 6), dtype=torch.float64, device=rows.device)
+    keep = torch.empty((n,), dtype=torch.int32, device=rows.device)
+    rc = L.load().toda_nusc_eval_prepare(L.ptr(rows), L.ptr(sample), L.ptr(cls), n, L.ptr(G), L.ptr(ego), n_samples, L.ptr(out),
+                                         L.ptr(keep), L.stream())
+    L.check(rc, "toda_nusc_eval_prepare")
+    return out, keep
+
+
+def nusc_eval_match(pred, score, pred_attr, gt, gt_attr, pred_off, gt_off, seg_cls, thresholds=NUSC_DIST_THS, tp_threshold=2):
+    """The nuScenes metric's matching (toda_nusc_eval_match) -> (match int32 [4, n_pred]: row of the matched ground truth or -1;
+    err fp64 [5, n_pred] at thresholds[tp_threshold]: trans, vel, scale, orient, attr, NaN where unmatched).  pred / gt fp64
+    [., 8] = centre x y, yaw, velocity x y, dx dy dz in segment order; pred_off / gt_off / seg_cls are HOST int32 arrays (CSR
+    offsets [n_seg + 1] and the class number of each segment)."""
+    lib = L.load()
+    pred, score, gt = (_eval_arg(t, torch.float64, "nusc_eval_match: boxes and scores") for t in (pred, score, gt))
+    pred_attr, gt_attr = (_eval_arg(t, torch.int32, "nusc_eval_match: attributes") for t in (pred_attr, gt_attr))
+    pred_off, gt_off, seg_cls = (np.ascontiguousarray(a, dtype=np.int32) for a in (pred_off, gt_off, seg_cls))
+    ths = np.ascontiguousarray(thresholds, dtype=np.float64)
+    n_pred, n_gt, n_seg = int(pred.shape[0]), int(gt.shape[0]), int(seg_cls.shape[0])
+    if pred.dim() != 2 or pred.shape[1] != 8 or gt.dim() != 2 or gt.shape[1] != 8:
+        raise RuntimeError("nusc_eval_match: pred and gt must be [., 8]")
+    if score.numel() != n_pred or pred_attr.numel() != n_pred or gt_attr.numel() != n_gt:
+        raise RuntimeError("nusc_eval_match: one score and one attribute per prediction, one attribute per ground truth")
+    if pred_off.shape != (n_seg + 1,) or gt_off.shape != (n_seg + 1,) or ths.shape != (4,):
+        raise RuntimeError("nusc_eval_match: offsets must be [n_seg + 1], and there are four thresholds")
+    dev = pred.device
+    match = torch.empty((4, n_pred), dtype=torch.int32, device=dev)
+    err = torch.empty((5, n_pred), dtype=torch.float64, device=dev)
+    ws_bytes = lib.toda_nusc_eval_match_workspace_bytes(n_seg)
+    ws = torch.empty((max(int(ws_bytes), 1),), dtype=torch.uint8, device=dev)
+    rc = lib.toda_nusc_eval_match(L.ptr(pred), L.ptr(score), L.ptr(pred_attr), n_pred, L.ptr(gt), L.ptr(gt_attr), n_gt,
+                                  pred_off.ctypes.data, gt_off.ctypes.data, seg_cls.ctypes.data, n_seg, ths.ctypes.data,
+                                  int(tp_threshold), L.ptr(match), L.ptr(err), L.ptr(ws), ws_bytes, L.stream())
+    L.check(rc, "toda_nusc_eval_match")
+    torch.cuda.current_stream().synchronize()           # the host offsets have been read once the copies into ws are done
+    return match, err
+
+
 class _CenterLoss(torch.autograd.Function):
     """CenterHead.get_loss of one head group in three launches forward / one backward (toda_center_loss_*).
     apply(n, hm_logits, reg_0..reg_{n-1}, heatmap, inds, mask, target_boxes, code_weights, cls_weight, loc_weight)

@@ -16,8 +16,9 @@ are CUDA tensors (`on_device`): build_dataloader then runs the dataset in the tr
 GPU.  With MAX_SWEEPS == 1 there is nothing to merge: the key frame stays numpy and reaches the device with the batch.
 get_lidar_with_sweeps_host is the same work in the reference's numpy arithmetic: the test oracle and the bench baseline.
 
-Out of scope, because they walk the nuScenes devkit's tables: the info builder (create_nuscenes_infos) and the devkit's NDS
-evaluator (eval_metric 'nuscenes' raises ImportError without the devkit).  eval_metric 'kitti' is served.
+Out of scope, because they walk the nuScenes devkit's tables: the info builder (create_nuscenes_infos) and the devkit's own
+evaluator (eval_metric 'nuscenes' raises ImportError without the devkit).  eval_metric 'kitti' is served, and eval_metric 'nds'
+is the nuScenes mAP / NDS by the project's evaluator (nuscenes_eval.py, matching on the device).
 
     python -m toda_amd.pcdet.datasets.nuscenes.nuscenes_dataset create_nuscenes_gt_database <dataset yaml> [--data_path DIR] [--version V]
 """
@@ -215,7 +216,9 @@ class NuScenesDataset(DatasetTemplate):
             return self.kitti_eval(copy.deepcopy(det_annos), copy.deepcopy(self.infos), class_names)
         if metric == "nuscenes":
             return self.nuscene_eval(det_annos, class_names, **kwargs)
-        raise NotImplementedError(f"eval_metric '{metric}': NuScenesDataset scores with 'kitti' (or 'nuscenes' through the nuScenes devkit)")
+        if metric == "nds":
+            return self.nds_eval(det_annos, class_names, **kwargs)
+        raise NotImplementedError(f"eval_metric '{metric}': NuScenesDataset scores with 'kitti', 'nds' (or 'nuscenes' through the nuScenes devkit)")
 
     def kitti_eval(self, eval_det_annos, eval_gt_annos, class_names):
         """The KITTI AP table in the LiDAR frame: detections and infos pair up by position, car / pedestrian / truck map to
@@ -247,6 +250,15 @@ class NuScenesDataset(DatasetTemplate):
             raise ImportError("eval_metric 'nuscenes' (NDS / mAP) runs the evaluator of the nuScenes devkit (package nuscenes-devkit, "
                               "module `nuscenes`), which is not installed; score with eval_metric 'kitti' instead") from e
         raise NotImplementedError("the nuScenes devkit evaluator is not wired up: score with eval_metric 'kitti'")
+
+    def nds_eval(self, det_annos, class_names, **kwargs):
+        """nuScenes mAP / NDS by the project's own evaluator (nuscenes_eval.py): results_nusc.json and metrics_summary.json under
+        output_path, the reference's report text and {trans_err, ..., mAP, NDS}."""
+        from . import nuscenes_eval
+        if kwargs.get("output_path", None) is None:
+            raise ValueError("eval_metric 'nds' writes results_nusc.json and metrics_summary.json: pass output_path")
+        return nuscenes_eval.evaluate(self.infos, det_annos, self.class_names if self.class_names else class_names, self.root_path,
+                                      self.dataset_cfg.VERSION, kwargs["output_path"], logger=self.logger)
 
     # ---- GT database: the frames through augmentor/database_sampler.create_groundtruth_database
     def create_groundtruth_database(self, used_classes=None, max_sweeps=10):
