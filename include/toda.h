@@ -675,6 +675,41 @@ int toda_sweeps_merge(const float* rows, int n, int n_sweeps, const int32_t* off
  * -1; n == 0 succeeds without a launch. */
 int toda_waymo_frame(const float* rows, int n, int c_in, int use_nlz, float* out, int32_t* flags, void* stream);
 
+/* Adversarial edit of one pseudo-labelled frame (csrc/adv_frame.hip; pcdet/datasets/nuscenes/nuscenes_mixup_adv_dataset.py
+ * get_ps_adv_lidar_with_sweeps, :191-274).
+ *   points [n, c] fp32, device, c >= 4: x, y, z, then the rest
+ *   table  [k, 10] doubles (cx cy cz dx dy dz rz op frac seed), once on the host (table_host: checked before anything is
+ *          launched) and once on the device (table_dev: what the kernels read); the box is rounded to fp32;
+ *          op 0 modify, 1 add, 2 remove, 3 nothing; frac in [0, 1); seed an integer below 2^32.
+ *          Contract: table_dev holds the same k * 10 doubles as table_host - the caller uploads the table it had checked
+ *          (ops.adv_edit builds one array and passes both).  The entry point cannot compare the two without a read-back, so
+ *          only table_host is validated; in a device copy that differs, an op outside 0..2 does not act, frac is clamped to
+ *          k_j in [0, c_j - 1] and the seed is converted to uint32 unchecked: a wrong edit, never an access out of bounds.
+ *   keys   [m] int64, device, sorted: linear voxel index (z * gy + y) * gx + x;   grads [m, 3] fp32, device
+ *   range_lo_host[3], voxel_host[3], grid_host[3] (x, y, z) and eps reach the kernels by value
+ * Row i:  g_i = grads[pos] where keys[pos] == key of cell floor((xyz - range_lo) / voxel) (fp32 subtraction and division), zero
+ *         outside the grid, for an absent key and with m == 0;  d_i = eps * g_i in fp32.
+ * Box j:  S_j = rows whose ORIGINAL x, y, z pass get_points_in_box (mode 1 of toda_points_in_boxes), c_j = |S_j|.  It acts when
+ *         op is 0 or 1 and c_j >= 1, or op is 2 and c_j > 5.  Then k_j = min(floor(frac * c_j), c_j - 1) (fp64 product) and T_j =
+ *         the c_j - k_j rows of S_j smallest in key_j(i) = fmix32(seed ^ uint32(i * 0x9E3779B9)) (murmur3's 32-bit finaliser;
+ *         the keys of a box differ pairwise).  Otherwise T_j is empty.
+ * A row walks the boxes in table order with cur = its original x, y, z; for i in T_j: modify cur -= d_i; add emits a row
+ * (cur - d_i, the other columns of row i); remove marks the row (it still takes part in later boxes).
+ * Output at dst[*cursor_dev ...]: the unmarked rows in order with their final cur, then the emitted rows in (i, j) order;
+ * *cursor_dev += their number; rows beyond cap_rows are dropped (the cursor still counts them, as toda_rows_select_append).
+ * counts [k] int32 = c_j.  A row with a NaN coordinate lies in no box and passes through.
+ * n == 0 or k == 0 succeed without a launch and write nothing: with k == 0 the output is the input.  c < 4, k above
+ * toda_adv_edit_max_boxes(), n * (k + 1) >= 2^31, a null host array, non-positive voxel or grid sizes, an op outside 0..3, a frac
+ * outside [0, 1), a seed that is no uint32, a workspace below toda_adv_edit_workspace_bytes(n, k) or a null device pointer return
+ * an error, in this order, before anything is launched.  The table is staged through LDS toda_adv_edit_chunk() boxes at a time. */
+int toda_adv_edit_max_boxes(void);
+int toda_adv_edit_chunk(void);
+size_t toda_adv_edit_workspace_bytes(int n, int k);
+int toda_adv_edit(const float* points, int n, int c, const double* table_host, const double* table_dev, int k,
+                  const int64_t* keys, const float* grads, int m, const float* range_lo_host, const float* voxel_host,
+                  const int32_t* grid_host, float eps, float* dst, int cap_rows, int32_t* cursor_dev, int32_t* counts,
+                  void* ws, size_t ws_bytes, void* stream);
+
 /* Forward convolution that also returns the BatchNorm statistics of its output (reference
  * pcdet/models/backbones_3d/spconv_backbone.py:21-25,54-64: every sparse conv is followed by BatchNorm1d): the
  * per-channel sum and sum of squares are taken from the accumulators in the kernel's epilogue, so the separate

@@ -140,6 +140,10 @@ SIGNATURES = {
     "toda_sweeps_merge_max_sweeps": (_i, []),
     "toda_sweeps_merge": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp]),
     "toda_waymo_frame": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "toda_adv_edit_max_boxes": (_i, []),
+    "toda_adv_edit_chunk": (_i, []),
+    "toda_adv_edit_workspace_bytes": (_sz, [_i, _i]),
+    "toda_adv_edit": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, C.c_float, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "toda_conv3x3_supported": (_i, [_i, _i, _i, _i, _i]),
     "toda_conv3x3_weight_floats": (_sz, [_i, _i]),
     "toda_conv3x3_transform_weight": (_i, [_vp, _i, _i, _i, _vp, _vp]),

@@ -2515,6 +2515,70 @@ def waymo_frame(rows, use_nlz=True):
     return out, flags
 
 
+ADV_COLS = 10              # cx cy cz dx dy dz rz op frac seed; op: 0 modify, 1 add, 2 remove, 3 nothing
+
+
+def adv_table(boxes, op, frac, seed):
+    """[k, 10] float64 host table of adv_edit from boxes [k, >= 7] and the per-box draws."""
+    boxes = np.asarray(boxes, np.float64)
+    boxes = boxes if boxes.ndim == 2 else boxes.reshape(-1, 7)
+    k = boxes.shape[0]
+    table = np.zeros((k, ADV_COLS), np.float64)
+    table[:, :7] = boxes[:, :7]
+    table[:, 7], table[:, 8], table[:, 9] = np.asarray(op, np.float64).reshape(k), np.asarray(frac, np.float64).reshape(k), np.asarray(seed, np.float64).reshape(k)
+    return table
+
+
+def adv_edit(points, boxes, op, frac, seed, keys, grads, voxel_cfg, eps, cap_rows=None, out=None):
+    """The adversarial edit of one pseudo-labelled frame on the device (C ABI: toda_adv_edit).  `points`: [n, c >= 4] fp32 device
+    rows.  Host side, per box: `boxes` [k, >= 7], `op` (0 modify, 1 add, 2 remove, 3 nothing), `frac` in [0, 1) and `seed` (uint32).
+    `keys`: sorted int64 [m] linear voxel indices and `grads` [m, 3] fp32 on the device (None / empty: no stored gradient).
+    voxel_cfg: dict with point_cloud_range and voxel_size (and grid_size in x, y, z order, else round((hi - lo) / voxel)).
+    Returns (edited cloud, counts int32 [k] = rows per box): the unmarked rows in order, then the added rows in (row, box)
+    order; the cloud's length costs one sync.  `cap_rows`: capacity of the result, an overflow raises (RowBuffer.finish); by
+    default 2 n rows, and a frame that needs more is edited again at its size.  `out`: a RowBuffer to append to instead - the
+    caller reads its cursor."""
+    lib = L.load()
+    points = points.contiguous()
+    n, c, _ = _rows(points, None)
+    table = adv_table(boxes, op, frac, seed)
+    k = table.shape[0]
+    counts = torch.zeros((k,), dtype=torch.int32, device=points.device)
+    if n == 0 or k == 0:
+        if out is not None:
+            out.append(points)
+            return out, counts
+        return points, counts
+    m = 0 if keys is None else int(keys.shape[0])
+    if m:
+        if keys.dtype != torch.int64 or grads.dtype != torch.float32 or grads.shape != (m, 3):
+            raise RuntimeError("adv_edit: keys int64 [m], grads float32 [m, 3]")
+        keys, grads = keys.contiguous(), grads.contiguous()
+    r = np.asarray(voxel_cfg["point_cloud_range"], np.float32)
+    v = np.asarray(voxel_cfg["voxel_size"], np.float32)
+    grid = voxel_cfg["grid_size"] if voxel_cfg.get("grid_size", None) is not None else grid_size_xyz(voxel_cfg["point_cloud_range"], voxel_cfg["voxel_size"])
+    buf = out if out is not None else RowBuffer(n * 2 if cap_rows is None else cap_rows, c, points.device)
+    if buf.data.shape[1] != c:
+        raise RuntimeError("adv_edit: column count differs")
+    th = L.host_f64(table.reshape(-1))
+    td = torch.from_numpy(table).to(points.device)
+    ws_bytes = lib.toda_adv_edit_workspace_bytes(n, k)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=points.device)
+    lo, vs, gs = L.host_f32(r[:3]), L.host_f32(v), L.host_i32(grid)
+    rc = lib.toda_adv_edit(L.ptr(points), n, c, L.hptr(th), L.ptr(td), k, L.ptr(keys) if m else None, L.ptr(grads) if m else None, m,
+                           L.hptr(lo), L.hptr(vs), L.hptr(gs), float(eps), L.ptr(buf.data), buf.cap, L.ptr(buf.cursor), L.ptr(counts),
+                           L.ptr(ws), ws_bytes, L.stream())
+    L.check(rc, "toda_adv_edit")
+    if out is not None:
+        return out, counts
+    if cap_rows is None:
+        total = int(buf.cursor.item())
+        if total > buf.cap:
+            return adv_edit(points, boxes, op, frac, seed, keys, grads, voxel_cfg, eps, cap_rows=total)
+        return buf.data[:total], counts
+    return buf.finish(), counts
+
+
 def points_polar_cell(points, phase, yaw_edges, dis_edges, dis_lo, dis_hi, n_dev=None):
     ye, de = L.host_f64(yaw_edges), L.host_f64(dis_edges)
     return _row_pass("toda_points_polar_cell", points, n_dev, -1, float(phase), L.hptr(ye), len(yaw_edges) - 1, L.hptr(de),

@@ -12,6 +12,7 @@ from ..utils import common_utils
 from .dataset import DatasetTemplate
 from .kitti.kitti_dataset import KittiDataset
 from .nuscenes.nuscenes_dataset import NuScenesDataset
+from .nuscenes.nuscenes_mixup_adv_dataset import NuScenesMixUpAdvDataset
 from .synthetic import SyntheticLidarDataset, SyntheticPairDataset
 from .mixup_dataset import SyntheticMixupPairDataset
 from .two_dataset import SyntheticMixDataset, WaymoNusMixDataset
@@ -21,6 +22,7 @@ __all__ = {
     "DatasetTemplate": DatasetTemplate,
     "KittiDataset": KittiDataset,
     "NuScenesDataset": NuScenesDataset,
+    "NuScenesMixUpAdvDataset": NuScenesMixUpAdvDataset,
     "WaymoDataset": WaymoDataset,
     "WaymoNusMixDataset": WaymoNusMixDataset,
     "WaymoNusPolarMixDataset": WaymoNusMixDataset,           # the reference's three names: MIX_TYPE decides which mix runs

@@ -25,6 +25,47 @@ from .processor.intra_domain_point_mixup import intra_domain_point_mixup_cd
 from .synthetic import SyntheticPairDataset
 
 
+def draw_mixup_indices(mixup_type, n, n_gt):
+    """The two frames of a MixUp item out of n frames, the first n_gt of them labelled: two np.random.randint calls."""
+    if mixup_type == "only_gt":
+        return np.random.randint(n_gt), np.random.randint(n_gt)
+    if mixup_type == "ps_gt":
+        return n_gt + np.random.randint(n - n_gt), np.random.randint(n_gt)
+    if mixup_type == "gt_gt+ps":
+        return np.random.randint(n_gt), np.random.randint(n)
+    if mixup_type == "gt+ps_gt+ps":
+        return np.random.randint(n), np.random.randint(n)
+    raise NotImplementedError(mixup_type)
+
+
+def encode_frame(dataset, data):
+    """Class filter + class-id column + feature encoding - what prepare_data does before the mix.  gt_names leave: from here on
+    the class of a box is column 7 of gt_boxes; every other key of `data` passes."""
+    names = data["gt_names"]
+    keep = np.array([n in dataset.class_names for n in names], dtype=bool)
+    ids = np.array([dataset.class_names.index(n) + 1 for n in names[keep]], dtype=np.float32).reshape(-1, 1)
+    out = {k: v for k, v in data.items() if k != "gt_names"}
+    out["gt_boxes"] = np.concatenate([data["gt_boxes"][keep], ids], axis=1).astype(np.float32)
+    return dataset.point_feature_encoder.forward(out)
+
+
+def finish_half(dataset, data):
+    """One half of a pair after the mix: DataAugmentor (records its transforms), then the processor queue.  The augmentor sees
+    boxes [n, 7] with their names and an all-true gt_boxes_mask, as prepare_data hands them over, so gt_sampling can paste; the
+    class-id column is rebuilt from the names that come back, which gives the pasted boxes theirs."""
+    if dataset.training and dataset.data_augmentor is not None:
+        names = np.array(dataset.class_names)[data["gt_boxes"][:, 7].astype(np.int64) - 1]
+        aug = dataset.data_augmentor.forward({"points": data["points"], "gt_boxes": data["gt_boxes"][:, :7].copy(), "gt_names": names,
+                                              "gt_boxes_mask": np.ones(len(names), dtype=bool)})
+        ids = np.array([dataset.class_names.index(n) + 1 for n in aug["gt_names"]], dtype=np.float32).reshape(-1, 1)
+        data.update(points=aug["points"], gt_boxes=np.concatenate([aug["gt_boxes"], ids], 1).astype(np.float32),
+                    augmentation_list=aug.get("augmentation_list", []), augmentation_params=aug.get("augmentation_params", {}))
+    else:
+        data.setdefault("augmentation_list", [])
+        data.setdefault("augmentation_params", {})
+    return dataset.data_processor.forward(data)
+
+
 class SyntheticMixupPairDataset(SyntheticPairDataset):
     def __init__(self, dataset_cfg, class_names, training=True, root_path=None, logger=None):
         super().__init__(dataset_cfg=dataset_cfg, class_names=class_names, training=training, root_path=root_path, logger=logger)
@@ -98,36 +139,14 @@ class SyntheticMixupPairDataset(SyntheticPairDataset):
 
     # ---- sampling policy --------------------------------------------------------------------
     def draw_mixup_indices(self):
-        n, n_gt = self.num_samples, self.num_gt
-        if self.mixup_type == "only_gt":
-            return np.random.randint(n_gt), np.random.randint(n_gt)
-        if self.mixup_type == "ps_gt":
-            return n_gt + np.random.randint(n - n_gt), np.random.randint(n_gt)
-        if self.mixup_type == "gt_gt+ps":
-            return np.random.randint(n_gt), np.random.randint(n)
-        if self.mixup_type == "gt+ps_gt+ps":
-            return np.random.randint(n), np.random.randint(n)
-        raise NotImplementedError(self.mixup_type)
+        return draw_mixup_indices(self.mixup_type, self.num_samples, self.num_gt)
 
     def _encode(self, data):
-        """Class filter + class-id column + feature encoding + upload - what prepare_data does before the mix."""
-        keep = np.array([n in self.class_names for n in data["gt_names"]], dtype=bool)
-        ids = np.array([self.class_names.index(n) + 1 for n in data["gt_names"][keep]], dtype=np.float32).reshape(-1, 1)
-        out = {"points": torch.from_numpy(data["points"]).cuda() if self.on_device else data["points"],
-               "gt_boxes": np.concatenate([data["gt_boxes"][keep], ids], axis=1).astype(np.float32), "frame_id": data["frame_id"]}
-        return self.point_feature_encoder.forward(out)
+        """encode_frame after the upload."""
+        return encode_frame(self, {**data, "points": torch.from_numpy(data["points"]).cuda() if self.on_device else data["points"]})
 
     def _finish(self, data):
-        """DataAugmentor (records its transforms) on boxes with the class column split off, then the processor queue."""
-        if self.training and self.data_augmentor is not None:
-            boxes, cls = data["gt_boxes"][:, :7].copy(), data["gt_boxes"][:, 7:]
-            aug = self.data_augmentor.forward({"points": data["points"], "gt_boxes": boxes})
-            data.update(points=aug["points"], gt_boxes=np.concatenate([aug["gt_boxes"], cls], 1).astype(np.float32),
-                        augmentation_list=aug.get("augmentation_list", []), augmentation_params=aug.get("augmentation_params", {}))
-        else:
-            data.setdefault("augmentation_list", [])
-            data.setdefault("augmentation_params", {})
-        return self.data_processor.forward(data)
+        return finish_half(self, data)
 
     def __getitem__(self, index):
         index = index % self.num_samples

@@ -209,6 +209,7 @@ class SyntheticPairDataset(SyntheticLidarDataset):
     which model_fn_decorator_cl undoes on the decoded boxes (reverse_transform)."""
 
     EPS = 1e-3
+    is_pair_dataset = True           # __getitem__ returns (adv, org): what the stage-2 consistency trainer takes
 
     def __getitem__(self, index):
         points, boxes, names = self.raw_sample(index)

@@ -4,6 +4,8 @@ tools/stage2_mixup_train_cl.py; its train_utils_cl module is missing from the re
 the loop below is written from model_fn_decorator_cl, pcdet/models/__init__.py:88-125).
 
     python -m toda_amd.tools.stage2_mixup_train_cl --cfg_file toda_amd/tools/cfgs/models/toda_stage1_centerpoint_res.yaml
+    python -m toda_amd.tools.stage2_mixup_train_cl --cfg_file toda_amd/tools/cfgs/models/toda_stage2_nus_advmix_real.yaml \
+        --pretrained_model <stage-1 ckpt> --pseudo_info_path <score_..._infos.pkl of generate_pseudo_labels --perturb>
 
 Both passes run inside one DistModel.forward so DDP issues one gradient all-reduce per step."""
 import os
@@ -73,15 +75,17 @@ def main(argv=None):
     bs = cfg.OPTIMIZATION.BATCH_SIZE_PER_GPU if args.batch_size is None else args.batch_size // total_gpus
     epochs = cfg.OPTIMIZATION.NUM_EPOCHS if args.epochs is None else args.epochs
     logger = common_utils.create_logger(None, rank=cfg.LOCAL_RANK)
-    # DATA_CONFIG.DATASET names a pair dataset (SyntheticMixupPairDataset: MixUp + adversarial frames, the TODA recipe);
-    # configs written for the single-frame datasets fall back to the plain (adv, org) pair of one frame
+    # DATA_CONFIG.DATASET names a pair dataset (class attribute is_pair_dataset - SyntheticMixupPairDataset and, on frames read
+    # from disk, NuScenesMixUpAdvDataset: MixUp + adversarial frames, the TODA recipe); configs written for the single-frame
+    # datasets fall back to the plain (adv, org) pair of one frame
     cls = dataset_registry.__all__.get(cfg.DATA_CONFIG.DATASET, SyntheticPairDataset)
-    if not issubclass(cls, SyntheticPairDataset):
+    if not getattr(cls, "is_pair_dataset", False):
         cls = SyntheticPairDataset
     dataset = cls(cfg.DATA_CONFIG, cfg.CLASS_NAMES, training=True)
     sampler = torch.utils.data.distributed.DistributedSampler(dataset) if dist_train else None
+    workers = 0 if getattr(dataset, "on_device", False) else args.workers      # items are CUDA tensors: the dataset stays in this process
     loader = torch.utils.data.DataLoader(dataset, batch_size=bs, shuffle=sampler is None, sampler=sampler,
-                                         num_workers=args.workers, collate_fn=dataset.collate_batch)
+                                         num_workers=workers, collate_fn=dataset.collate_batch)
     model = build_network(cfg.MODEL, len(cfg.CLASS_NAMES), dataset).cuda()
     optimizer = build_optimizer(model, cfg.OPTIMIZATION)
     wrapped = DistModel(model)

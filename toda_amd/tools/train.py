@@ -42,6 +42,8 @@ def parse_config(argv=None):
     p.add_argument("--merge_all_iters_to_one_epoch", action="store_true", default=False)
     p.add_argument("--output_dir", type=str, default=None)
     p.add_argument("--backend", type=str, default="nccl")
+    p.add_argument("--pseudo_info_path", type=str, default=None,
+                   help="stage 2: the infos file of tools/generate_pseudo_labels (sets DATA_CONFIG.PSEUDO_INFO_PATH)")
     p.add_argument("--set", dest="set_cfgs", default=None, nargs=argparse.REMAINDER)
     args = p.parse_args(argv)
     cfg_from_yaml_file(args.cfg_file, cfg)
@@ -49,6 +51,8 @@ def parse_config(argv=None):
     cfg.EXP_GROUP_PATH = "/".join(args.cfg_file.split("/")[1:-1])
     if args.set_cfgs is not None:
         cfg_from_list(args.set_cfgs, cfg)
+    if args.pseudo_info_path is not None:
+        cfg.DATA_CONFIG.PSEUDO_INFO_PATH = args.pseudo_info_path
     return args, cfg
 
 
