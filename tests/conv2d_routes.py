@@ -3,11 +3,11 @@ work split a shape takes: the pixel-GEMMs of toda_amd/csrc/gemm2d.hip (stride-2 
 and the Winograd F(4x4,3x3) convolution of toda_amd/csrc/conv2d.hip.  Every function mirrors one host-side rule of those files;
 test_conv2d_routes.py holds the restatement against the library's own size and support queries.
 
-A pixel-GEMM launch is (r1 rows, r2 columns, gz contraction splits):
-  path "split"   pg_split_grid: pg_gemm_split_kernel (128 x 128 tiles) for every grid whose contraction is at least one stage
+A pixel-GEMM launch (pg_launch) is (r1 rows, r2 columns, gz contraction splits):
+  path "split"   pg_kernel<PgSplit> (128 x 128 tiles) for every grid whose contraction is at least one stage
                  (kc >= PG_K); shorter ones take the native kernels
-  path "native"  pg_small: pg_gemm_kernel<64> when gz == 1 and there are fewer than 768 tiles of 128 x 128, else <128>;
-                 the stride-2 data gradient has its own switch (4 parity classes in blockIdx.z counted in the tiles)."""
+  path "native"  pg_kernel<PgFp32<64>> when gz == 1 and there are fewer than 768 tiles of 128 x 128, else <PgFp32<128>>;
+                 the stride-2 data gradient's 4 parity classes in blockIdx.z are counted in the tiles."""
 
 N_CU = 256          # compute units of an MI355X: the stream-K grids below are sized by it
 
@@ -45,7 +45,7 @@ def pg_splits(n_pixels, tiles, target=PG_WG_TARGET):
 
 
 def pg_kernel(path, r1, r2, gz, kc):
-    """Kernel of PG_LAUNCH for an r1 x r2 result contracting kc values: "split", "native64" or "native128"."""
+    """Kernel of pg_launch for an r1 x r2 result contracting kc values: "split", "native64" or "native128"."""
     if path == "split" and kc >= PG_K:
         return "split"
     return "native64" if gz == 1 and cdiv(r1, 128) * cdiv(r2, 128) < 768 else "native128"

@@ -143,7 +143,7 @@ def test_pixel_gemm_cases_reach_the_shape_edges():
         r = routes("native", *case)
         assert r["fwd"] == "native128" and r["dgrad"] == "native128" and r["pixels"] >= E.GATE_MIN_OUTPUTS
     # contractions shorter than one stage stay on the fp32 kernels under the split path: the 3-channel deblocks whose forward broke the
-    # split path's error gate (1.9-2.1 x the fp32 kernel's rms) before pg_split_grid looked at the contraction
+    # split path's error gate (1.9-2.1 x the fp32 kernel's rms) before pg_launch looked at the contraction
     for case in (E.DECONV_CASES[4], E.DECONV_CASES[11]):
         assert case[1] < R.PG_K and R.deconv_routes("split", *case)["fwd"] == "native64", case
     # the split-count switch: the large target reaches the 512 cap, the small one a single split

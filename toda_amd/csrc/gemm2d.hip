@@ -4,11 +4,13 @@
 // and out, on the fp32 matrix cores - in round 2 these ran on MIOpen / rocBLAS (implicit-GEMM + transposes, GEMM + im2col / col2im:
 // 1.2 ms of an 18 ms step, 23 launches).
 //
-// One kernel core: C[R1 x R2] += O1[R1 x c] . O2[R2 x c]^T over tiles of 128 x 128 x 16, 4 waves of 64 x 64
-// (v_mfma_f32_16x16x4_f32, 16 accumulator tiles per wave), operands staged through LDS as [row][16 contraction values] so that a
-// lane's fragment of FOUR MFMA steps is one ds_read_b128 (the k-permutation of spconv.hip: lane group g holds contraction indices
-// 4g..4g+3, step j contracts over {4g'+j}), register-staged double buffering.  What differs between the nine GEMMs is only how an
-// operand element is found in memory and where a result element goes - "accessors":
+// One kernel (pg_kernel) and one launch function (pg_launch) around two tile products, C[R1 x R2] += O1[R1 x c] . O2[R2 x c]^T:
+// pg_tile<T> on the fp32 matrix cores - tiles of 128 x 128 (or 64 x 64) x 32, 4 waves of 64 x 64 (v_mfma_f32_16x16x4_f32, 16
+// accumulator tiles per wave), operands staged through LDS as [row][contraction values] so that a lane's fragment of FOUR MFMA steps
+// is one ds_read_b128 (the k-permutation of spconv.hip: lane group g holds contraction indices 4g..4g+3, step j contracts over
+// {4g'+j}), register-staged double buffering - and pg_tile_split, the same product on the bf16 matrix pipe (matrix path "split",
+// described at the function).  Both take the same accessors: what differs between the nine GEMMs is only how an operand element is
+// found in memory and where a result element goes:
 //   forward / data gradient: O1 = weights (rows = produced channels), O2 = pixels of the map (rows = pixels, contraction = gathered
 //     channels x taps); the pixel index mapping carries the stride-2 gather, the pixel shuffle of the transposed convolution (as an
 //     epilogue store: no separate shuffle pass) and the parity classes of the stride-2 data gradient (an input pixel reaches only the
@@ -16,6 +18,9 @@
 //   weight gradient: both operands are maps, the contraction runs over pixels, split over workgroups into slabs that a second
 //     kernel adds in fixed order (deterministic, no float atomics).
 #include <stdlib.h>
+
+#include <type_traits>
+#include <utility>
 
 #include "common.h"
 #include "split_common.cuh"
@@ -35,6 +40,28 @@ constexpr int PG_BLOCK = 256;
 // of these kernels, not bytes: no division by a run-time value inside the loop.  Out-of-range elements read as 0.
 
 struct NoCur {};      // (operands without a pixel cursor, see RowCur)
+
+// Pixel n of a [B][rows][width] grid: decomposed ONCE (one division pair), the pixels after it follow by carry.  An image taken as one
+// row of hw pixels is set(n, hw) and next(1, hw).
+struct PixWalk {
+    int b, y, x;
+    __device__ __forceinline__ void set(int n, int width) {
+        b = n / width;
+        y = 0;
+        x = n - b * width;
+    }
+    __device__ __forceinline__ void set(int n, int rows, int width) {
+        set(n, rows * width);
+        y = x / width;
+        x -= y * width;
+    }
+    __device__ __forceinline__ void next(int rows, int width) {
+        if (++x == width) {
+            x = 0;
+            if (++y == rows) y = 0, ++b;
+        }
+    }
+};
 
 // dense matrix with strides: element (r, c) = p[r * sr + c * sc]
 template <bool COLSHAPE>
@@ -89,12 +116,10 @@ struct PixPlain {
         bool vec;
     };
     __device__ __forceinline__ void init(State& s, int n) const {
-        int b = n / hw, pix = n - b * hw;          // ONE division; the other seven pixels follow by carry
+        PixWalk p;
+        p.set(n, hw);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            s.off[i] = b < B ? (long long)b * C * hw + pix : -1;
-            if (++pix == hw) pix = 0, ++b;
-        }
+        for (int i = 0; i < 8; ++i, p.next(1, hw)) s.off[i] = p.b < B ? (long long)p.b * C * hw + p.x : -1;
         // two aligned groups of four pixels inside one image each
         s.vec = (hw & 3) == 0 && s.off[0] >= 0 && s.off[7] >= 0 && s.off[3] == s.off[0] + 3 && s.off[7] == s.off[4] + 3;
     }
@@ -199,24 +224,19 @@ struct ChanPlain {
     }
     __device__ __forceinline__ void load(const State& s, int n, float (&v)[8]) const {
         const bool ok = s.ch < C;
-        const int b0 = n / hw, p0 = n - b0 * hw;          // (one division per stage and thread; the 8 pixels follow by carry)
+        PixWalk p;          // (one division per stage and thread)
+        p.set(n, hw);
         if ((hw & 3) == 0) {
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                int b = b0, pix = p0 + 4 * h;
-                if (pix >= hw) pix -= hw, ++b;
+            for (int h = 0; h < 2; ++h) {          // n is a multiple of 8: two aligned groups of four pixels, each inside one image
                 pg4 t = pg4{0.f, 0.f, 0.f, 0.f};
-                if (ok && b < B) t = *reinterpret_cast<const pg4*>(x + ((long long)b * C + s.ch) * hw + pix);
+                if (ok && p.b < B) t = *reinterpret_cast<const pg4*>(x + ((long long)p.b * C + s.ch) * hw + p.x);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) v[4 * h + i] = t[i];
+                for (int i = 0; i < 4; ++i, p.next(1, hw)) v[4 * h + i] = t[i];
             }
         } else {
 #pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                int b = b0, pix = p0 + i;
-                while (pix >= hw) pix -= hw, ++b;
-                v[i] = (ok && b < B) ? x[((long long)b * C + s.ch) * hw + pix] : 0.0f;
-            }
+            for (int i = 0; i < 8; ++i, p.next(1, hw)) v[i] = (ok && p.b < B) ? x[((long long)p.b * C + s.ch) * hw + p.x] : 0.0f;
         }
     }
 };
@@ -238,6 +258,9 @@ struct PixConvS2 {          // rows = output pixels, contraction = (ci, ky, kx)
         unsigned ok, top, left;   // bit i: pixel valid / oy == 0 / ox == 0
     };
     __device__ __forceinline__ void init(State& s, int n) const {
+        // PixWalk's walk written out: through the struct the fp32 kernels of the stride-2 forward got an s_waitcnt vmcnt(0) between the two
+        // operands' loads of every stage (162-163 us against 157-159 on the 128 -> 256 layer at 188 x 188: "rejected variant 1" of
+        // profiles/gemm2d_one_loop_bench.txt)
         const int howo = g.Ho * g.Wo;
         s.ok = s.top = s.left = 0u;
         int b = n / howo;
@@ -304,18 +327,12 @@ struct TapConvS2 {          // rows = (ci, ky, kx), contraction = output pixels 
         for (int i = 0; i < 8; ++i) v[i] = ((m >> i) & 1u) ? g.x[(i < p.jw ? ea : eb) + 2 * i] : 0.0f;
     }
     __device__ __forceinline__ void load(const State& s, int n, float (&v)[8]) const {
-        const int howo = g.Ho * g.Wo;
-        int b = n / howo;
-        const int rem = n - b * howo;
-        int oy = rem / g.Wo, ox = rem - oy * g.Wo;
+        PixWalk p;          // (b, oy, ox)
+        p.set(n, g.Ho, g.Wo);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const bool in = s.ok && b < g.B && !(s.ky == 0 && oy == 0) && !(s.kx == 0 && ox == 0);
-            v[i] = in ? g.x[((long long)b * g.C * g.H + 2 * oy) * g.W + 2 * ox + s.d] : 0.0f;
-            if (++ox == g.Wo) {
-                ox = 0;
-                if (++oy == g.Ho) oy = 0, ++b;
-            }
+        for (int i = 0; i < 8; ++i, p.next(g.Ho, g.Wo)) {
+            const bool in = s.ok && p.b < g.B && !(s.ky == 0 && p.y == 0) && !(s.kx == 0 && p.x == 0);
+            v[i] = in ? g.x[((long long)p.b * g.C * g.H + 2 * p.y) * g.W + 2 * p.x + s.d] : 0.0f;
         }
     }
 };
@@ -335,6 +352,8 @@ struct PixUnshuffle {       // rows = low-resolution pixels, contraction = (co, 
         unsigned ok;
     };
     __device__ __forceinline__ void init(State& s, int n) const {
+        // PixWalk's walk written out, as in PixConvS2::init: through the struct the carries became branches, 41 instructions more in front
+        // of the stage loop; this way the three kernels are the parent's code ("rejected variant 2" of profiles/gemm2d_one_loop_bench.txt)
         const int hw = g.h * g.w;
         s.ok = 0u;
         int b = n / hw;
@@ -389,18 +408,11 @@ struct ChanUnshuffle {      // rows = (co, i, j), contraction = low-resolution p
         for (int i = 0; i < 8; ++i) v[i] = ((m >> i) & 1u) ? g.dy[(i < p.jw ? ea : eb) + 2 * i] : 0.0f;
     }
     __device__ __forceinline__ void load(const State& s, int n, float (&v)[8]) const {
-        const int hw = g.h * g.w;
-        int b = n / hw;
-        const int rem = n - b * hw;
-        int y = rem / g.w, x = rem - y * g.w;
+        PixWalk p;
+        p.set(n, g.h, g.w);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            v[i] = (s.ok && b < g.B) ? g.dy[((long long)b * g.C * (2 * g.h) + 2 * y) * (2 * g.w) + 2 * x + s.d] : 0.0f;
-            if (++x == g.w) {
-                x = 0;
-                if (++y == g.h) y = 0, ++b;
-            }
-        }
+        for (int i = 0; i < 8; ++i, p.next(g.h, g.w))
+            v[i] = (s.ok && p.b < g.B) ? g.dy[((long long)p.b * g.C * (2 * g.h) + 2 * p.y) * (2 * g.w) + 2 * p.x + s.d] : 0.0f;
     }
 };
 
@@ -428,19 +440,14 @@ struct PixS2Dgrad {         // rows = input pixels of the class (b, y', x'), con
     __device__ __forceinline__ void init(State& s, int n) const {
         const int hh = H / 2, ww = W / 2;
         s.ok = s.bottom = s.right = 0u;
-        int b = n / (hh * ww);
-        const int rem = n - b * (hh * ww);
-        int yy = rem / ww, xx = rem - yy * ww;
+        PixWalk p;          // (b, y', x')
+        p.set(n, hh, ww);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            s.off[i] = ((long long)b * Cout * Ho + yy) * Wo + xx;
-            s.ok |= (unsigned)(b < B) << i;
-            s.bottom |= (unsigned)(yy + 1 >= Ho) << i;
-            s.right |= (unsigned)(xx + 1 >= Wo) << i;
-            if (++xx == ww) {
-                xx = 0;
-                if (++yy == hh) yy = 0, ++b;
-            }
+        for (int i = 0; i < 8; ++i, p.next(hh, ww)) {
+            s.off[i] = ((long long)p.b * Cout * Ho + p.y) * Wo + p.x;
+            s.ok |= (unsigned)(p.b < B) << i;
+            s.bottom |= (unsigned)(p.y + 1 >= Ho) << i;
+            s.right |= (unsigned)(p.x + 1 >= Wo) << i;
         }
     }
     __device__ __forceinline__ void load(const State& s, int k, float (&v)[8]) const {
@@ -484,6 +491,7 @@ struct WS2Dgrad {           // rows = ci, contraction = (co, tap of the class): 
 // ---- result stores: column n of the tile product is decomposed once (prep), then its 16 rows are written (put) ------------------
 struct StoreNCHW {          // r1 = channel m, r2 = pixel n = b * hw + pix
     static constexpr bool ROWS4 = true;      // four consecutive r2 of one r1 are four consecutive floats when hw % 4 == 0
+    static constexpr int CLASSES = 1;        // blockIdx.z = contraction split (4 in StoreS2Class: parity class)
     float* y;
     int M, N, hw;
     __device__ __forceinline__ bool vec_ok() const { return (hw & 3) == 0 && (N & 3) == 0; }
@@ -492,8 +500,9 @@ struct StoreNCHW {          // r1 = channel m, r2 = pixel n = b * hw + pix
     }
     __device__ __forceinline__ long long prep(int n) const {
         if (n >= N) return -1;
-        const int b = n / hw, pix = n - b * hw;
-        return (long long)b * M * hw + pix;
+        PixWalk p;
+        p.set(n, hw);
+        return (long long)p.b * M * hw + p.x;
     }
     __device__ __forceinline__ void put(long long base, int m, float v) const {
         if (base >= 0 && m < M) y[base + (long long)m * hw] = v;
@@ -501,14 +510,14 @@ struct StoreNCHW {          // r1 = channel m, r2 = pixel n = b * hw + pix
 };
 struct StoreShuffle {       // r1 = (co, i, j), r2 = (b, y, x) of the low-resolution map: y_out[b][co][2y + i][2x + j]
     static constexpr bool ROWS4 = false;
+    static constexpr int CLASSES = 1;
     float* y;
     int M, N, C, h, w;
     __device__ __forceinline__ long long prep(int n) const {
         if (n >= N) return -1;
-        const int hw = h * w;
-        const int b = n / hw, rem = n - b * hw;
-        const int yy = rem / w, xx = rem - yy * w;
-        return ((long long)b * C * (2 * h) + 2 * yy) * (2 * w) + 2 * xx;
+        PixWalk p;
+        p.set(n, h, w);
+        return ((long long)p.b * C * (2 * h) + 2 * p.y) * (2 * w) + 2 * p.x;
     }
     __device__ __forceinline__ void put(long long base, int m, float v) const {
         if (base >= 0 && m < M) {
@@ -519,14 +528,14 @@ struct StoreShuffle {       // r1 = (co, i, j), r2 = (b, y, x) of the low-resolu
 };
 struct StoreS2Class {       // r1 = ci, r2 = (b, y', x') of the class: dx[b][ci][2y' + py][2x' + px]
     static constexpr bool ROWS4 = false;
+    static constexpr int CLASSES = 4;
     float* dx;
     int M, N, H, W, py, px;
     __device__ __forceinline__ long long prep(int n) const {
         if (n >= N) return -1;
-        const int hh = H / 2, ww = W / 2;
-        const int b = n / (hh * ww), rem = n - b * (hh * ww);
-        const int yy = rem / ww, xx = rem - yy * ww;
-        return ((long long)b * M * H + 2 * yy + py) * W + 2 * xx + px;
+        PixWalk p;
+        p.set(n, H / 2, W / 2);
+        return ((long long)p.b * M * H + 2 * p.y + py) * W + 2 * p.x + px;
     }
     __device__ __forceinline__ void put(long long base, int m, float v) const {
         if (base >= 0 && m < M) dx[base + (long long)m * H * W] = v;
@@ -534,6 +543,7 @@ struct StoreS2Class {       // r1 = ci, r2 = (b, y', x') of the class: dx[b][ci]
 };
 struct StoreSlab {          // weight gradients: partial sums of contraction split z -> slab[z][r1][r2]
     static constexpr bool ROWS4 = true;
+    static constexpr int CLASSES = 1;
     float* slab;
     int M, N;
     __device__ __forceinline__ bool vec_ok() const { return (N & 3) == 0; }
@@ -718,10 +728,7 @@ __device__ __forceinline__ void pg_tile(const Op1& o1, const Op2& o2, const Stor
 // index of the same rows: one DPP row rotation hands each of them the other's half, both pack 4 rows x (k, k + 1) and store one
 // 16-byte line; fragment = four conflict-free ds_read_b32 per plane.  Both layouts give lane group g the contraction indices
 // 8 g .. 8 g + 7 in order.
-// 128 x 128 tiles only, 512 threads: the three planes of both operands, double buffered, are 100-123 KiB of LDS = ONE workgroup per
-// CU; with 256 threads that is one wave per SIMD and a wave's fetch -> split -> store -> barrier -> matrix work runs with nothing
-// beside it (measured: no faster than the fp32 form).  Eight waves share the images (2 per SIMD): wave (wm, wn) owns 64 x 32 of the tile.
-constexpr int PGS_BLOCK = 512;
+// 128 x 128 tiles only, eight waves (PgSplit::BLOCK) share the images: wave (wm, wn) owns 64 x 32 of the tile.
 template <class Op1, class Op2, class Store>
 __device__ __forceinline__ void pg_tile_split(const Op1& o1, const Op2& o2, const Store& st, int c_begin, int c_end) {
     static_assert(PG_K == 32, "one bf16 matrix-instruction depth per stage");
@@ -888,42 +895,46 @@ __device__ __forceinline__ void pg_tile_split(const Op1& o1, const Op2& o2, cons
     }
 }
 
-template <class Op1, class Op2, class Store>
-__global__ void __launch_bounds__(PGS_BLOCK)
-pg_gemm_split_kernel(const Op1 o1, const Op2 o2, const Store st, int c_total, int c_per_split) {
-    const int c_begin = blockIdx.z * c_per_split;
-    const int c_end = min(c_total, c_begin + c_per_split);
-    pg_tile_split(o1, o2, st, c_begin, c_end > c_begin ? c_end : c_begin);      // (an empty split still owns a slab: it stores zeros)
-}
+// ---- one kernel, one launch ---------------------------------------------------------------------------------------------------------
+// What the kernel and its launch need to know of a tile product ("math"): workgroup size, tile rows, and which loop runs.  The two
+// loops and their epilogues above stay apart: written as one loop over a policy, and already with only the epilogue shared, the same
+// arithmetic compiled to other schedules - the bits the same, the stride-2 forward and data gradient 4-9 % slower on the split path
+// (profiles/gemm2d_one_loop_bench.txt) - so that merge waits for a change that owns those kernels' timing.
+template <int TILE>
+struct PgFp32 {
+    static constexpr int BLOCK = PG_BLOCK, T = TILE;
+    template <class Op1, class Op2, class Store>
+    __device__ __forceinline__ static void tile(const Op1& o1, const Op2& o2, const Store& st, int c_begin, int c_end) {
+        pg_tile<TILE>(o1, o2, st, c_begin, c_end);
+    }
+};
+struct PgSplit {
+    // 512 threads: the three planes of both operands, double buffered, are 100-123 KiB of LDS = ONE workgroup per CU; with 256 threads
+    // that is one wave per SIMD and a wave's fetch -> split -> store -> barrier -> matrix work runs with nothing beside it (measured:
+    // no faster than the fp32 form).  With eight waves there are 2 per SIMD.
+    static constexpr int BLOCK = 512, T = 128;
+    template <class Op1, class Op2, class Store>
+    __device__ __forceinline__ static void tile(const Op1& o1, const Op2& o2, const Store& st, int c_begin, int c_end) {
+        pg_tile_split(o1, o2, st, c_begin, c_end);
+    }
+};
 
-__global__ void __launch_bounds__(PGS_BLOCK)
-pg_s2_dgrad_split_kernel(WS2Dgrad o1, PixS2Dgrad o2, StoreS2Class st) {
-    S2Class c;
-    c.set(blockIdx.z);
-    o1.c = c;
-    o2.c = c;
-    st.py = c.py, st.px = c.px;
-    pg_tile_split(o1, o2, st, 0, o2.Cout << (c.lty + c.ltx));
-}
-
-template <int T, class Op1, class Op2, class Store>
-__global__ void __launch_bounds__(PG_BLOCK)
-pg_gemm_kernel(const Op1 o1, const Op2 o2, const Store st, int c_total, int c_per_split) {
-    const int c_begin = blockIdx.z * c_per_split;
-    const int c_end = min(c_total, c_begin + c_per_split);
-    pg_tile<T>(o1, o2, st, c_begin, c_end > c_begin ? c_end : c_begin);      // (an empty split still owns a slab: it stores zeros)
-}
-
-// stride-2 data gradient: blockIdx.z = parity class
-template <int T>
-__global__ void __launch_bounds__(PG_BLOCK)
-pg_s2_dgrad_kernel(WS2Dgrad o1, PixS2Dgrad o2, StoreS2Class st) {
-    S2Class c;
-    c.set(blockIdx.z);
-    o1.c = c;
-    o2.c = c;
-    st.py = c.py, st.px = c.px;
-    pg_tile<T>(o1, o2, st, 0, o2.Cout << (c.lty + c.ltx));
+template <class Math, class Op1, class Op2, class Store>
+__global__ void __launch_bounds__(Math::BLOCK)
+pg_kernel(Op1 o1, Op2 o2, Store st, int c_total, int c_per_split) {
+    int c_begin = 0, c_end;
+    if constexpr (Store::CLASSES > 1) {      // blockIdx.z = parity class, each with its own contraction length
+        S2Class c;
+        c.set(blockIdx.z);
+        o1.c = c;
+        o2.c = c;
+        st.py = c.py, st.px = c.px;
+        c_end = c_total << (c.lty + c.ltx);
+    } else {                                 // blockIdx.z = contraction split
+        c_begin = blockIdx.z * c_per_split;
+        c_end = max(c_begin, min(c_total, c_begin + c_per_split));      // (an empty split still owns a slab: it stores zeros)
+    }
+    Math::tile(o1, o2, st, c_begin, c_end);
 }
 
 __global__ void __launch_bounds__(PG_BLOCK)
@@ -943,8 +954,30 @@ pg_slab_reduce_kernel(const float* __restrict__ slab, int splits, long long elem
     out[e] = s;
 }
 
+// One GEMM launch: an r1 x r2 result contracting kc values, in `splits` chunks of c_per_split over grid z (1 = the whole contraction),
+// or once per parity class of the store.
+//   matrix path "split" (toda_set_matrix_path): PgSplit for every grid, also those that fill the 256 CUs badly at 128 x 128 (278 tiles:
+//     the stride-2 forward 149 us against 157 on the fp32 form, the 2 x 2 deblock's data gradient 125 against 129); 128 x 64 tiles for
+//     those measured slower (156 / 132).  Contractions shorter than one stage (kc < PG_K: a deblock fed by 3 channels, a stride-2 layer
+//     producing fewer than 32) stay on the fp32 kernels, as the sparse gather-GEMMs do below 32 channels: with a handful of products
+//     per output the dropped cross terms of the split are no longer small against fp32's own rounding (a 3-channel deblock forward
+//     measured 1.9-2.1 x the fp32 kernel's rms error).
+//   otherwise 128-row fp32 tiles when they fill the chip (or when contraction splits do: the weight gradients), 64-row tiles when not.
+template <class Op1, class Op2, class Store>
+static void pg_launch(const Op1& o1, const Op2& o2, const Store& st, long long r1, long long r2, int splits, int kc, int c_per_split, void* stream) {
+    auto go = [&](auto math) {
+        typedef decltype(math) Math;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(pg_kernel<Math, Op1, Op2, Store>), dim3(cdiv(r2, Math::T), cdiv(r1, Math::T), splits * Store::CLASSES),
+                           dim3(Math::BLOCK), 0, (hipStream_t)stream, o1, o2, st, kc, c_per_split);
+    };
+    if (toda_matrix_path() == 1 && kc >= PG_K) go(PgSplit{});
+    else if (splits == 1 && (long long)cdiv(r1, 128) * cdiv(r2, 128) * Store::CLASSES < 768) go(PgFp32<64>{});
+    else go(PgFp32<128>{});
+}
+
+// ---- weight gradients: dw as an r1 x r2 matrix, the contraction over n pixels split over workgroups into slabs ---------------------
 static int pg_splits(long long n_pixels, int tiles) {
-    // weight gradients: the output is a few tiles, the parallelism comes from splitting the pixels - about 512 workgroups = the
+    // the output is a few tiles, the parallelism comes from splitting the pixels - about 512 workgroups = the
     // 256 CUs x 2 resident slots filled once (equal-length chunks: 768 workgroups were two rounds for one and a half rounds of work -
     // stride-2 conv wgrad 182 -> 167 us, the deblocks' 82 / 156 -> 81 / 156; TODA_PG_WG_TARGET), contraction chunks of at least 8 stages
     static const int target = getenv("TODA_PG_WG_TARGET") ? atoi(getenv("TODA_PG_WG_TARGET")) : 512;
@@ -957,32 +990,40 @@ static int pg_splits(long long n_pixels, int tiles) {
     return want;
 }
 
-// 128-row tiles when they fill the chip (or when contraction splits do: gz > 1, the weight gradients), 64-row tiles otherwise
-static inline bool pg_small(long long r1, long long r2, int gz) { return gz == 1 && (long long)cdiv(r1, 128) * cdiv(r2, 128) < 768; }
-// matrix path "split" (toda_set_matrix_path): the same accessors and stores around pg_tile_split - 128 x 128 tiles, one 512-thread
-// workgroup per CU.  Also for the grids that fill the 256 CUs badly at that tile size (278 tiles: the stride-2 forward 149 us against 157
-// on the fp32 form, the 2 x 2 deblock's data gradient 125 against 129); 128 x 64 tiles for those measured slower (156 / 132).
-// Contractions shorter than one stage (kc < PG_K: a deblock fed by 3 channels, a stride-2 layer producing fewer than 32) stay on the fp32
-// kernels, as the sparse gather-GEMMs do below 32 channels: with a handful of products per output the dropped cross terms of the split
-// are no longer small against fp32's own rounding (a 3-channel deblock forward measured 1.9-2.1 x the fp32 kernel's rms error).
-static inline bool pg_split_grid(long long r1, long long r2, int gz, long long kc) {
-    if (toda_matrix_path() != 1 || kc < PG_K) return false;
-    static const int env = getenv("TODA_PG_SPLIT") ? atoi(getenv("TODA_PG_SPLIT")) : 1;
-    (void)r1, (void)r2, (void)gz;
-    return env != 0;
+struct PgWgradPlan {
+    int splits, per;          // contraction chunks and their length (whole stages)
+    size_t ws_bytes;          // slab[splits][r1][r2]
+};
+static PgWgradPlan pg_wgrad_plan(long long n, int r1, int r2) {
+    PgWgradPlan p;
+    p.splits = pg_splits(n, cdiv(r1, 128) * cdiv(r2, 128));
+    p.per = cdiv(cdiv(n, p.splits), PG_K) * PG_K;
+    p.ws_bytes = align_up((size_t)p.splits * r1 * r2 * sizeof(float), 256);
+    return p;
 }
-#define PG_LAUNCH(O1, O2, ST, r1, r2, gz, a1, a2, as, kc, ...)                                                                             \
-    do {                                                                                                                                   \
-        if (pg_split_grid(r1, r2, gz, kc))                                                                                                 \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(pg_gemm_split_kernel<O1, O2, ST>), dim3(cdiv(r2, 128), cdiv(r1, 128), gz), dim3(PGS_BLOCK), 0, \
-                               (hipStream_t)stream, a1, a2, as, kc, __VA_ARGS__);                                                          \
-        else if (pg_small(r1, r2, gz))                                                                                                     \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(pg_gemm_kernel<64, O1, O2, ST>), dim3(cdiv(r2, 64), cdiv(r1, 64), gz), dim3(PG_BLOCK), 0,   \
-                               (hipStream_t)stream, a1, a2, as, kc, __VA_ARGS__);                                                          \
-        else                                                                                                                               \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(pg_gemm_kernel<128, O1, O2, ST>), dim3(cdiv(r2, 128), cdiv(r1, 128), gz), dim3(PG_BLOCK), 0, \
-                               (hipStream_t)stream, a1, a2, as, kc, __VA_ARGS__);                                                          \
-    } while (0)
+
+// ops(std::bool_constant<FAST>) gives the two operands in their FAST or plain form; FAST needs 32-bit element offsets (map_elems) and
+// the geometry the operands' fast_ok ask for.  The slabs are added in split order by a second kernel (deterministic, no float atomics).
+template <class Ops>
+static int pg_wgrad(const char* who, int n, int r1, int r2, long long map_elems, bool fast_geom, Ops&& ops, float* dw, void* ws, size_t ws_bytes,
+                    void* stream) {
+    const PgWgradPlan plan = pg_wgrad_plan(n, r1, r2);
+    if (ws_bytes < plan.ws_bytes) {
+        set_error("%s: workspace too small", who);
+        return TODA_EWORKSPACE;
+    }
+    StoreSlab st{(float*)ws, r1, r2};
+    auto go = [&](auto fast) {
+        const auto o = ops(fast);
+        pg_launch(o.first, o.second, st, r1, r2, plan.splits, n, plan.per, stream);
+    };
+    if (map_elems < (1LL << 31) && fast_geom) go(std::true_type{});
+    else go(std::false_type{});
+    const long long elems = (long long)r1 * r2;
+    hipLaunchKernelGGL(pg_slab_reduce_kernel, dim3(cdiv(elems, PG_BLOCK)), dim3(PG_BLOCK), 0, (hipStream_t)stream, (const float*)ws, plan.splits, elems, dw);
+    TODA_LAUNCH_CHECK();
+    return TODA_OK;
+}
 
 static int pg_check(const char* who, int B, int Cin, int Cout, int H, int W) {
     TODA_CHECK_ARG(B >= 1 && Cin >= 1 && Cout >= 1 && H >= 1 && W >= 1, "%s: bad shape", who);
@@ -1006,7 +1047,7 @@ extern "C" int toda_conv3x3s2_fwd(const float* x, const float* w, int batch, int
     MatOp<false> o1{w, cout, K, K, 1};
     PixConvS2 o2{ConvS2Geom{x, batch, cin, H, W, Ho, Wo}};
     StoreNCHW st{y, cout, N, Ho * Wo};
-    PG_LAUNCH(MatOp<false>, PixConvS2, StoreNCHW, cout, N, 1, o1, o2, st, K, K);
+    pg_launch(o1, o2, st, cout, N, 1, K, K, stream);
     TODA_LAUNCH_CHECK();
     return TODA_OK;
 }
@@ -1018,20 +1059,13 @@ extern "C" int toda_conv3x3s2_dgrad(const float* dy, const float* w, int batch, 
     WS2Dgrad o1{w, cin, cout, S2Class{}};
     PixS2Dgrad o2{dy, batch, cout, H, W, H / 2, W / 2, S2Class{}};
     StoreS2Class st{dx, cin, N, H, W, 0, 0};
-    if (pg_split_grid(cin, N, 4, cout))      // (the one-tap class contracts cout values)
-        hipLaunchKernelGGL(pg_s2_dgrad_split_kernel, dim3(cdiv(N, 128), cdiv(cin, 128), 4), dim3(PGS_BLOCK), 0, (hipStream_t)stream, o1, o2, st);
-    else if ((long long)cdiv(cin, 128) * cdiv(N, 128) * 4 < 768)
-        hipLaunchKernelGGL(pg_s2_dgrad_kernel<64>, dim3(cdiv(N, 64), cdiv(cin, 64), 4), dim3(PG_BLOCK), 0, (hipStream_t)stream, o1, o2, st);
-    else
-        hipLaunchKernelGGL(pg_s2_dgrad_kernel<128>, dim3(cdiv(N, 128), cdiv(cin, 128), 4), dim3(PG_BLOCK), 0, (hipStream_t)stream, o1, o2, st);
+    pg_launch(o1, o2, st, cin, N, 1, cout, 0, stream);      // (the one-tap class contracts cout values, the others 2 and 4 cout)
     TODA_LAUNCH_CHECK();
     return TODA_OK;
 }
 
 extern "C" size_t toda_conv3x3s2_wgrad_workspace_bytes(int batch, int cin, int cout, int H, int W) {
-    const long long n = (long long)batch * (H / 2) * (W / 2);
-    const int splits = pg_splits(n, cdiv(cin * 9, 128) * cdiv(cout, 128));
-    return align_up((size_t)splits * cout * cin * 9 * sizeof(float), 256);
+    return pg_wgrad_plan((long long)batch * (H / 2) * (W / 2), cout, cin * 9).ws_bytes;
 }
 
 extern "C" int toda_conv3x3s2_wgrad(const float* x, const float* dy, int batch, int cin, int cout, int H, int W, float* dw, void* ws, size_t ws_bytes,
@@ -1039,27 +1073,14 @@ extern "C" int toda_conv3x3s2_wgrad(const float* x, const float* dy, int batch, 
     TODA_CHECK_ARG(x && dy && dw && ws && toda_conv3x3s2_supported(batch, cin, cout, H, W), "conv3x3s2_wgrad: null pointer or odd map");
     if (int rc = pg_check("conv3x3s2_wgrad", batch, cin, cout, H, W)) return rc;
     const int Ho = H / 2, Wo = W / 2, N = batch * Ho * Wo, K = cin * 9;
-    const int splits = pg_splits(N, cdiv(K, 128) * cdiv(cout, 128));
-    if (ws_bytes < toda_conv3x3s2_wgrad_workspace_bytes(batch, cin, cout, H, W)) {
-        set_error("conv3x3s2_wgrad: workspace too small");
-        return TODA_EWORKSPACE;
-    }
-    int per = cdiv(cdiv(N, splits), PG_K) * PG_K;
-    StoreSlab st{(float*)ws, cout, K};
-    const bool small_map = (long long)batch * (cin > cout ? cin : cout) * H * W < (1LL << 31);      // 32-bit element offsets in the FAST accessors
-    if (small_map && ChanPlain<true>::fast_ok(Ho * Wo) && TapConvS2<true>::fast_ok(Wo)) {
-        ChanPlain<true> o1{dy, batch, cout, Ho * Wo};                       // rows co, contraction pixels
-        TapConvS2<true> o2{ConvS2Geom{x, batch, cin, H, W, Ho, Wo}, K};   // rows (ci, ky, kx)
-        PG_LAUNCH(ChanPlain<true>, TapConvS2<true>, StoreSlab, cout, K, splits, o1, o2, st, N, per);
-    } else {
-        ChanPlain<false> o1{dy, batch, cout, Ho * Wo};
-        TapConvS2<false> o2{ConvS2Geom{x, batch, cin, H, W, Ho, Wo}, K};
-        PG_LAUNCH(ChanPlain<false>, TapConvS2<false>, StoreSlab, cout, K, splits, o1, o2, st, N, per);
-    }
-    const long long elems = (long long)cout * K;
-    hipLaunchKernelGGL(pg_slab_reduce_kernel, dim3(cdiv(elems, PG_BLOCK)), dim3(PG_BLOCK), 0, (hipStream_t)stream, (const float*)ws, splits, elems, dw);
-    TODA_LAUNCH_CHECK();
-    return TODA_OK;
+    return pg_wgrad(
+        "conv3x3s2_wgrad", N, cout, K, (long long)batch * (cin > cout ? cin : cout) * H * W, ChanPlain<true>::fast_ok(Ho * Wo) && TapConvS2<true>::fast_ok(Wo),
+        [&](auto fast) {
+            constexpr bool F = decltype(fast)::value;
+            return std::make_pair(ChanPlain<F>{dy, batch, cout, Ho * Wo},                           // rows co, contraction pixels
+                                  TapConvS2<F>{ConvS2Geom{x, batch, cin, H, W, Ho, Wo}, K});      // rows (ci, ky, kx)
+        },
+        dw, ws, ws_bytes, stream);
 }
 
 // --------------------------------------------- ConvTranspose2d(Cin, Cout, k = s, stride = s), s in {1, 2}: base_bev_backbone.py:47-66
@@ -1074,13 +1095,8 @@ extern "C" int toda_deconv_fwd(const float* x, const float* w, int batch, int ci
     const int N = batch * H * W, M = cout * s * s;
     MatOp<true> o1{w, M, cin, 1, M};          // element (m, k) = w[k][m]: rows contiguous
     PixPlain o2{x, batch, cin, H * W};
-    if (s == 1) {
-        StoreNCHW st{y, cout, N, H * W};
-        PG_LAUNCH(MatOp<true>, PixPlain, StoreNCHW, M, N, 1, o1, o2, st, cin, cin);
-    } else {
-        StoreShuffle st{y, M, N, cout, H, W};
-        PG_LAUNCH(MatOp<true>, PixPlain, StoreShuffle, M, N, 1, o1, o2, st, cin, cin);
-    }
+    if (s == 1) pg_launch(o1, o2, StoreNCHW{y, cout, N, H * W}, M, N, 1, cin, cin, stream);
+    else pg_launch(o1, o2, StoreShuffle{y, M, N, cout, H, W}, M, N, 1, cin, cin, stream);
     TODA_LAUNCH_CHECK();
     return TODA_OK;
 }
@@ -1091,22 +1107,14 @@ extern "C" int toda_deconv_dgrad(const float* dy, const float* w, int batch, int
     const int N = batch * H * W, K = cout * s * s;
     MatOp<false> o1{w, cin, K, K, 1};         // element (ci, k) = w[ci][k]
     StoreNCHW st{dx, cin, N, H * W};
-    if (s == 1) {
-        PixPlain o2{dy, batch, cout, H * W};
-        PG_LAUNCH(MatOp<false>, PixPlain, StoreNCHW, cin, N, 1, o1, o2, st, K, K);
-    } else {
-        PixUnshuffle o2{UnshuffleGeom{dy, batch, cout, H, W}};
-        PG_LAUNCH(MatOp<false>, PixUnshuffle, StoreNCHW, cin, N, 1, o1, o2, st, K, K);
-    }
+    if (s == 1) pg_launch(o1, PixPlain{dy, batch, cout, H * W}, st, cin, N, 1, K, K, stream);
+    else pg_launch(o1, PixUnshuffle{UnshuffleGeom{dy, batch, cout, H, W}}, st, cin, N, 1, K, K, stream);
     TODA_LAUNCH_CHECK();
     return TODA_OK;
 }
 
 extern "C" size_t toda_deconv_wgrad_workspace_bytes(int batch, int cin, int cout, int H, int W, int s) {
-    const long long n = (long long)batch * H * W;
-    const int K = cout * s * s;
-    const int splits = pg_splits(n, cdiv(K, 128) * cdiv(cin, 128));
-    return align_up((size_t)splits * cin * K * sizeof(float), 256);
+    return pg_wgrad_plan((long long)batch * H * W, cin, cout * s * s).ws_bytes;
 }
 
 extern "C" int toda_deconv_wgrad(const float* x, const float* dy, int batch, int cin, int cout, int H, int W, int s, float* dw, void* ws, size_t ws_bytes,
@@ -1114,32 +1122,17 @@ extern "C" int toda_deconv_wgrad(const float* x, const float* dy, int batch, int
     TODA_CHECK_ARG(x && dy && dw && ws && toda_deconv_supported(batch, cin, cout, H, W, s), "deconv_wgrad: null pointer or stride not in {1, 2}");
     if (int rc = pg_check("deconv_wgrad", batch, cin, cout, H * s, W * s)) return rc;
     const int N = batch * H * W, K = cout * s * s;
-    const int splits = pg_splits(N, cdiv(K, 128) * cdiv(cin, 128));
-    if (ws_bytes < toda_deconv_wgrad_workspace_bytes(batch, cin, cout, H, W, s)) {
-        set_error("deconv_wgrad: workspace too small");
-        return TODA_EWORKSPACE;
-    }
-    int per = cdiv(cdiv(N, splits), PG_K) * PG_K;
-    StoreSlab st{(float*)ws, cin, K};
-    const bool small_map = (long long)batch * (cin > cout ? cin : cout) * H * s * W * s < (1LL << 31);      // 32-bit element offsets in the FAST accessors
-    const bool fast = small_map && ChanPlain<true>::fast_ok(H * W) && (s == 1 || ChanUnshuffle<true>::fast_ok(W));
-    if (s == 1 && fast) {
-        ChanPlain<true> o1{x, batch, cin, H * W}, o2{dy, batch, cout, H * W};                           // rows ci / co, contraction pixels
-        PG_LAUNCH(ChanPlain<true>, ChanPlain<true>, StoreSlab, cin, K, splits, o1, o2, st, N, per);
-    } else if (s == 1) {
-        ChanPlain<false> o1{x, batch, cin, H * W}, o2{dy, batch, cout, H * W};
-        PG_LAUNCH(ChanPlain<false>, ChanPlain<false>, StoreSlab, cin, K, splits, o1, o2, st, N, per);
-    } else if (fast) {
-        ChanPlain<true> o1{x, batch, cin, H * W};
-        ChanUnshuffle<true> o2{UnshuffleGeom{dy, batch, cout, H, W}, K};
-        PG_LAUNCH(ChanPlain<true>, ChanUnshuffle<true>, StoreSlab, cin, K, splits, o1, o2, st, N, per);
-    } else {
-        ChanPlain<false> o1{x, batch, cin, H * W};
-        ChanUnshuffle<false> o2{UnshuffleGeom{dy, batch, cout, H, W}, K};
-        PG_LAUNCH(ChanPlain<false>, ChanUnshuffle<false>, StoreSlab, cin, K, splits, o1, o2, st, N, per);
-    }
-    const long long elems = (long long)cin * K;
-    hipLaunchKernelGGL(pg_slab_reduce_kernel, dim3(cdiv(elems, PG_BLOCK)), dim3(PG_BLOCK), 0, (hipStream_t)stream, (const float*)ws, splits, elems, dw);
-    TODA_LAUNCH_CHECK();
-    return TODA_OK;
+    const long long map_elems = (long long)batch * (cin > cout ? cin : cout) * H * s * W * s;
+    const bool fast_geom = ChanPlain<true>::fast_ok(H * W) && (s == 1 || ChanUnshuffle<true>::fast_ok(W));
+    // x: rows ci, contraction pixels;  dy: rows co (s = 1) or (co, i, j) (s = 2)
+    auto ops1 = [&](auto fast) {
+        constexpr bool F = decltype(fast)::value;
+        return std::make_pair(ChanPlain<F>{x, batch, cin, H * W}, ChanPlain<F>{dy, batch, cout, H * W});
+    };
+    auto ops2 = [&](auto fast) {
+        constexpr bool F = decltype(fast)::value;
+        return std::make_pair(ChanPlain<F>{x, batch, cin, H * W}, ChanUnshuffle<F>{UnshuffleGeom{dy, batch, cout, H, W}, K});
+    };
+    if (s == 1) return pg_wgrad("deconv_wgrad", N, cin, K, map_elems, fast_geom, ops1, dw, ws, ws_bytes, stream);
+    return pg_wgrad("deconv_wgrad", N, cin, K, map_elems, fast_geom, ops2, dw, ws, ws_bytes, stream);
 }
