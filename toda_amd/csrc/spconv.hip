@@ -145,6 +145,194 @@ __device__ __forceinline__ void gather_rows(__amdgpu_buffer_rsrc_t rsrc, int cg,
     }
 }
 
+// ---- pieces the kernels below and those of spconv_split.cuh share ------------------------------------------------------------------
+// All forced inline, register arrays by reference and indexed by unrolled loops only, so nothing leaves the registers.  The lane
+// coordinates (r / ii = lane & 15, g = lane >> 4, lane) are ARGUMENTS, taken at the top of the kernel as they always were: derived
+// inside a helper they are computed at its call, their live ranges end up elsewhere and a third of the kernels change occupancy.
+// Two pieces stay written out in a kernel because the helper compiled to other resources there (profiles/spconv_shared_resources.txt):
+// the prologue in gather_gemm_kernel and the fold of the waves in the two weight-gradient kernels.
+//
+// Tile prologue of the LDS and split gather-GEMMs (gather_gemm_kernel has the same text): accumulators start at the bias (lane (r, g):
+// the NT produced channels NT r .. NT r + NT - 1), lane r holds the (possibly permuted) output row of position r of each of the wave's
+// RT tiles.  Rows past the end are clamped to the last row, so that the id loads stay unconditional, and are never stored.
+template <int RT, int NT>
+__device__ __forceinline__ void gg_prologue(const float* bias, int cp, int row0, int n_out, const int* order, int r,
+                                            f32x4 (&acc)[RT][NT], int (&rows)[RT], bool (&live)[RT]) {
+#pragma unroll
+    for (int n = 0; n < NT; ++n) {
+        float b = 0.0f;
+        if (bias && NT * r + n < cp) b = bias[NT * r + n];
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) acc[rt][n] = f32x4{b, b, b, b};
+    }
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+        live[rt] = row0 + rt * 16 + r < n_out;
+        rows[rt] = live[rt] ? (order ? order[row0 + rt * 16 + r] : row0 + rt * 16 + r) : n_out - 1;
+    }
+}
+
+// Output rows of a wave: D holds row 4 g + reg of a tile in register reg, a lane's NT accumulators of it are NT consecutive channels.
+template <int RT, int NT>
+__device__ __forceinline__ void gg_store_rows(const f32x4 (&acc)[RT][NT], const int (&rows)[RT], int row0, int n_out, int cp,
+                                              float* out, int r, int g) {
+    const bool full = cp == 16 * NT;
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            const int pos = row0 + rt * 16 + 4 * g + reg;
+            const int row = __shfl(rows[rt], 4 * g + reg, 64);  // lane r' holds the (possibly permuted) row of tile position r'
+            if (pos >= n_out) continue;
+            float* dst = out + (size_t)row * cp + NT * r;
+            if (full) {
+                if constexpr (NT == 1) {
+                    dst[0] = acc[rt][0][reg];
+                } else if constexpr (NT == 2) {
+                    *reinterpret_cast<float2*>(dst) = make_float2(acc[rt][0][reg], acc[rt][1][reg]);
+                } else {
+#pragma unroll
+                    for (int n = 0; n < NT; n += 4)
+                        *reinterpret_cast<f32x4*>(dst + n) =
+                            f32x4{acc[rt][n][reg], acc[rt][n + 1][reg], acc[rt][n + 2][reg], acc[rt][n + 3][reg]};
+                }
+            } else {
+#pragma unroll
+                for (int n = 0; n < NT; ++n)
+                    if (NT * r + n < cp) dst[n] = acc[rt][n][reg];
+            }
+        }
+    }
+}
+
+// BatchNorm statistics of the layer's output, taken from the accumulators (reference spconv_backbone.py:21-25: every conv
+// of post_act_block / SparseBasicBlock is followed by BatchNorm1d): per-channel sum and sum of squares of this workgroup's
+// rows -> stats scratch [2 cp][gridDim.x] behind the 2 cp results, folded in fixed order by fold_partials_kernel.  fp32
+// over the <= 8 values of a lane and the 4 lane groups, fp64 across waves and workgroups (as toda_rows_moments).
+// Holds a workgroup barrier: every wave of the workgroup calls it, the ones whose rows are all past the end included.
+template <int NT, int RT, int WAVES>
+__device__ __forceinline__ void gg_moments(float (*st_sh)[2][16 * NT], int wv, int blk, const f32x4 (&acc)[RT][NT], int row0, int n_out,
+                                           int cp, double* stats, int r, int g) {
+    float sm[NT], sq[NT];
+#pragma unroll
+    for (int n = 0; n < NT; ++n) {
+        sm[n] = sq[n] = 0.0f;
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg)
+                if (row0 + rt * 16 + 4 * g + reg < n_out) {
+                    const float v = acc[rt][n][reg];
+                    sm[n] += v;
+                    sq[n] += v * v;
+                }
+        sm[n] += __shfl_xor(sm[n], 16, 64);
+        sq[n] += __shfl_xor(sq[n], 16, 64);
+        sm[n] += __shfl_xor(sm[n], 32, 64);
+        sq[n] += __shfl_xor(sq[n], 32, 64);
+        if (g == 0) {
+            st_sh[wv][0][NT * r + n] = sm[n];
+            st_sh[wv][1][NT * r + n] = sq[n];
+        }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < 2 * cp) {
+        const int qq = threadIdx.x / cp, ch = threadIdx.x - qq * cp;
+        double a = 0.0;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) a += (double)st_sh[w][qq][ch];
+        stats[2 * cp + (size_t)(qq * cp + ch) * gridDim.x + blk] = a;
+    }
+}
+
+// Block id of a weight-gradient grid -> (row chunk, offset[, channel sub-block: SUB]).  The K offset-blocks of a chunk read the same
+// dout rows and neighbouring input rows: they are given consecutive slots of ONE XCD (workgroup ids are dealt round-robin over the 8
+// XCDs, so XCD x owns ids x, x + 8, ...) and run side by side out of that XCD's L2.  With the offset as the slow grid axis (round 1)
+// the blocks of a chunk were on one XCD too, but a whole grid pass apart in time: PMC 1.50 GB from HBM per launch of the 32 -> 32
+// layer at 682 k rows against 0.27 GB algorithmic.  xcd_chunks < 0 (TODA_WG_XCD=0): plain order.  The launch pads the chunk count to a multiple of 8.
+template <bool SUB>
+__device__ __forceinline__ int wg_block(int xcd_chunks, int K, int& chunk, int& k) {      // returns the sub-block (0 without SUB)
+    const int n_chunks = xcd_chunks < 0 ? -xcd_chunks : xcd_chunks;
+    const int nsub_blk = SUB ? (int)gridDim.x / (n_chunks * K) : 1;
+    const int b = blockIdx.x;
+    if (xcd_chunks > 0) {
+        const int xcd = b & 7, t = (b >> 3) / K;
+        k = (b >> 3) - t * K;
+        chunk = (t / nsub_blk) * 8 + xcd;
+        return t % nsub_blk;
+    }
+    chunk = b % n_chunks;
+    k = SUB ? (b / n_chunks) % K : b / n_chunks;
+    return SUB ? b / (n_chunks * K) : 0;
+}
+
+// The pair walk of a wave of a weight-gradient kernel over the rows base0, base0 + bstep, ... < row_end of one offset (nbr_k = its
+// column of the table), 64 rows at a time: the neighbour ids of the NEXT 64 rows are requested before this batch's rounds run, so
+// their latency is covered by those rounds; the valid (in, out) pairs are compacted (ballot + prefix popcount) into the wave's two
+// queues as BYTE offsets of the rows (multiplied once, when a pair is queued: a 32-bit multiply is a quarter-rate instruction on the
+// lanes the MFMAs use); round(d, limit, tag) contracts the queue entries [d, d + ROUND), full rounds with full_tag; the tail
+// (< ROUND entries) moves to the front of the queue, and what is left after the last batch is one partial round.
+template <int ROUND, class FullTag, class Round>
+__device__ __forceinline__ void wg_pair_walk(int* qi, int* qo, int base0, int row_end, int bstep, const int* nbr_k, int n_out,
+                                             unsigned row_a, unsigned row_b, int lane, FullTag full_tag, Round&& round) {
+    int qn = 0;  // wave-uniform queue length (< ROUND between batches)
+    int iv_next = nbr_k[min(base0 + lane, n_out - 1)];  // clamped, unconditional
+    for (int base = base0; base < row_end; base += bstep) {
+        const int o = base + lane;
+        const int iv = iv_next;
+        iv_next = nbr_k[min(o + bstep, n_out - 1)];
+        const int i = o < row_end ? iv : -1;
+        const unsigned long long vote = __ballot(i >= 0);
+        if (vote == 0) continue;
+        if (i >= 0) {
+            const int pos = qn + __popcll(vote & ((1ull << lane) - 1));
+            qi[pos] = (int)((unsigned)i * row_a);
+            qo[pos] = (int)((unsigned)o * row_b);
+        }
+        qn += __popcll(vote);
+        __builtin_amdgcn_wave_barrier();
+        int done = 0;
+        while (qn - done >= ROUND) {
+            round(done, qn, full_tag);
+            done += ROUND;
+        }
+        const int left = qn - done;
+        if (done > 0 && left > 0) {  // move the tail to the front of the queue
+            int ti = 0, to = 0;
+            if (lane < left) {
+                ti = qi[done + lane];
+                to = qo[done + lane];
+            }
+            __builtin_amdgcn_wave_barrier();
+            if (lane < left) {
+                qi[lane] = ti;
+                qo[lane] = to;
+            }
+        }
+        qn = left;
+        __builtin_amdgcn_wave_barrier();
+    }
+    if (qn > 0) round(0, qn, std::false_type{});
+}
+
+// A wave's (MTB x NTB)-tile block at tile (m0, n0) of offset k -> the chunk's slab [cout][K][cin].
+// D: col = lane & 15 -> cout tile column, row = 4 (lane >> 4) + reg -> cin tile row.  BOUND: channel counts that are not 16 x tiles.
+template <bool BOUND, int MTB, int NTB>
+__device__ __forceinline__ void wg_store_slab(const f32x4 (&acc)[MTB][NTB], float* slab, int chunk, int k, int K, int MT, int NT,
+                                              int m0, int n0, int cin, int cout, int ii, int g) {
+    float* dst = slab + (size_t)chunk * cout * K * cin;
+#pragma unroll
+    for (int m = 0; m < MTB; ++m)
+#pragma unroll
+        for (int n = 0; n < NTB; ++n)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                const int ci = MT * (4 * g + reg) + m0 + m;
+                const int co = NT * ii + n0 + n;
+                if (!BOUND || (ci < cin && co < cout)) dst[((size_t)co * K + k) * cin + ci] = acc[m][n][reg];
+            }
+}
+
 // Data gradient of a STRIDED convolution.  Input site i reaches output o = (i + pad - k) / stride only for the kernel offsets k with
 // k = i + pad (mod stride) on every axis: a fine voxel has 1, 2, 4 or 8 CANDIDATE offsets out of 27 (27 / 8 on average - exactly
 // the pair density of these tables), fixed by the residues of its coordinates, and every candidate exists (the output set holds
@@ -171,6 +359,7 @@ gather_gemm_kernel(const float* __restrict__ in, int n_in, int cg, const float* 
     const int row0 = wave * (16 * RT);
     if (row0 >= n_out) return;  // wave-uniform
 
+    // gg_prologue written out: through the helper the NT >= 4 forms of this kernel compile to 10-36 fewer registers and another occupancy
     f32x4 acc[RT][NT];
 #pragma unroll
     for (int n = 0; n < NT; ++n) {
@@ -266,34 +455,7 @@ gather_gemm_kernel(const float* __restrict__ in, int n_in, int cg, const float* 
     } else {
         for (int k = 0; k < K; ++k) offset(k);
     }
-
-    const bool full = cp == 16 * NT;
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-            const int pos = row0 + rt * 16 + 4 * g + reg;
-            const int row = __shfl(rows[rt], 4 * g + reg, 64);  // lane r' holds the (possibly permuted) row of tile position r'
-            if (pos >= n_out) continue;
-            float* dst = out + (size_t)row * cp + NT * r;
-            if (full) {
-                if constexpr (NT == 1) {
-                    dst[0] = acc[rt][0][reg];
-                } else if constexpr (NT == 2) {
-                    *reinterpret_cast<float2*>(dst) = make_float2(acc[rt][0][reg], acc[rt][1][reg]);
-                } else {
-#pragma unroll
-                    for (int n = 0; n < NT; n += 4)
-                        *reinterpret_cast<f32x4*>(dst + n) =
-                            f32x4{acc[rt][n][reg], acc[rt][n + 1][reg], acc[rt][n + 2][reg], acc[rt][n + 3][reg]};
-                }
-            } else {
-#pragma unroll
-                for (int n = 0; n < NT; ++n)
-                    if (NT * r + n < cp) dst[n] = acc[rt][n][reg];
-            }
-        }
-    }
+    gg_store_rows<RT, NT>(acc, rows, row0, n_out, cp, out, r, g);
 }
 
 // Row blocks -> XCDs.  The hardware deals workgroup ids round-robin over the 8 XCDs, each with a private 4 MiB L2: with the
@@ -347,21 +509,10 @@ gather_gemm_lds_kernel(const float* __restrict__ in, int n_in, int cg, const flo
     const f32x4* __restrict__ wp4 = reinterpret_cast<const f32x4*>(wp);
 
     f32x4 acc[RT][NT];
-#pragma unroll
-    for (int n = 0; n < NT; ++n) {
-        float b = 0.0f;
-        if (bias && NT * r + n < cp) b = bias[NT * r + n];
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) acc[rt][n] = f32x4{b, b, b, b};
-    }
-    const __amdgpu_buffer_rsrc_t in_rsrc = table_rsrc(in, (unsigned)n_in * (unsigned)cg * 4u);
     int rows[RT];
     bool live[RT];
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-        live[rt] = row0 + rt * 16 + r < n_out;
-        rows[rt] = live[rt] ? (order ? order[row0 + rt * 16 + r] : row0 + rt * 16 + r) : n_out - 1;
-    }
+    gg_prologue<RT, NT>(bias, cp, row0, n_out, order, r, acc, rows, live);
+    const __amdgpu_buffer_rsrc_t in_rsrc = table_rsrc(in, (unsigned)n_in * (unsigned)cg * 4u);
 
     // stage offset 0
 #pragma unroll
@@ -448,73 +599,13 @@ gather_gemm_lds_kernel(const float* __restrict__ in, int n_in, int cg, const flo
         }
         __syncthreads();
     }
-    if (row0 >= n_out && !stats) return;
+    if (row0 >= n_out && !stats) return;      // with statistics the waves past the end still meet the barrier of gg_moments
 
-    // BatchNorm statistics of the layer's output, taken from the accumulators (reference spconv_backbone.py:21-25: every conv
-    // of post_act_block / SparseBasicBlock is followed by BatchNorm1d): per-channel sum and sum of squares of this workgroup's
-    // rows -> stats scratch [2 cp][gridDim.x] behind the 2 cp results, folded in fixed order by fold_partials_kernel.  fp32
-    // over the <= 8 values of a lane and the 4 lane groups, fp64 across waves and workgroups (as toda_rows_moments).
     if (stats) {
         __shared__ float st_sh[BLK / 64][2][16 * NT];
-        float sm[NT], sq[NT];
-#pragma unroll
-        for (int n = 0; n < NT; ++n) {
-            sm[n] = sq[n] = 0.0f;
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-                for (int reg = 0; reg < 4; ++reg)
-                    if (row0 + rt * 16 + 4 * g + reg < n_out) {
-                        const float v = acc[rt][n][reg];
-                        sm[n] += v;
-                        sq[n] += v * v;
-                    }
-            sm[n] += __shfl_xor(sm[n], 16, 64);
-            sq[n] += __shfl_xor(sq[n], 16, 64);
-            sm[n] += __shfl_xor(sm[n], 32, 64);
-            sq[n] += __shfl_xor(sq[n], 32, 64);
-            if (g == 0) {
-                st_sh[threadIdx.x >> 6][0][NT * r + n] = sm[n];
-                st_sh[threadIdx.x >> 6][1][NT * r + n] = sq[n];
-            }
-        }
-        __syncthreads();
-        if ((int)threadIdx.x < 2 * cp) {
-            const int qq = threadIdx.x / cp, ch = threadIdx.x - qq * cp;
-            double a = 0.0;
-#pragma unroll
-            for (int w = 0; w < BLK / 64; ++w) a += (double)st_sh[w][qq][ch];
-            stats[2 * cp + (size_t)(qq * cp + ch) * gridDim.x + blk] = a;
-        }
+        gg_moments<NT, RT, BLK / 64>(st_sh, threadIdx.x >> 6, blk, acc, row0, n_out, cp, stats, r, g);
     }
-
-    const bool full = cp == 16 * NT;
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-            const int pos = row0 + rt * 16 + 4 * g + reg;
-            const int row = __shfl(rows[rt], 4 * g + reg, 64);  // lane r' holds the (possibly permuted) row of tile position r'
-            if (pos >= n_out) continue;
-            float* dst = out + (size_t)row * cp + NT * r;
-            if (full) {
-                if constexpr (NT == 1) {
-                    dst[0] = acc[rt][0][reg];
-                } else if constexpr (NT == 2) {
-                    *reinterpret_cast<float2*>(dst) = make_float2(acc[rt][0][reg], acc[rt][1][reg]);
-                } else {
-#pragma unroll
-                    for (int n = 0; n < NT; n += 4)
-                        *reinterpret_cast<f32x4*>(dst + n) =
-                            f32x4{acc[rt][n][reg], acc[rt][n + 1][reg], acc[rt][n + 2][reg], acc[rt][n + 3][reg]};
-                }
-            } else {
-#pragma unroll
-                for (int n = 0; n < NT; ++n)
-                    if (NT * r + n < cp) dst[n] = acc[rt][n][reg];
-            }
-        }
-    }
+    gg_store_rows<RT, NT>(acc, rows, row0, n_out, cp, out, r, g);
 }
 
 // wgrad: dW[co][k][ci] = sum_o in[nbr[k][o]][ci] * dout[o][co].  Grid (row chunk, offset, channel
@@ -545,27 +636,9 @@ wgrad_kernel(const float* __restrict__ in, int n_in, int cin, const float* __res
     __shared__ int q_in[SC_BLOCK / 64][QCAP], q_out[SC_BLOCK / 64][QCAP];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int ii = lane & 15, g = lane >> 4;
-    // 1-D grid over (row chunk, offset, channel sub-block).  The K offset-blocks of a chunk read the same dout rows and neighbouring
-    // input rows: they are given consecutive slots of ONE XCD (workgroup ids are dealt round-robin over the 8 XCDs, so XCD x owns
-    // ids x, x + 8, ...) and run side by side out of that XCD's L2.  With the offset as the slow grid axis (round 1) the blocks
-    // of a chunk were on one XCD too, but a whole grid pass apart in time: PMC 1.50 GB from HBM per launch of the 32 -> 32
-    // layer at 682 k rows against 0.27 GB algorithmic.  xcd_chunks < 0 (TODA_WG_XCD=0): plain order.  The launch pads the chunk count to a multiple of 8.
-    const int n_chunks = xcd_chunks < 0 ? -xcd_chunks : xcd_chunks;
-    const int nsub_blk = (int)gridDim.x / (n_chunks * K);
-    int chunk, k, sub_blk;
-    {
-        const int b = blockIdx.x;
-        if (xcd_chunks > 0) {
-            const int xcd = b & 7, t = (b >> 3) / K;
-            k = (b >> 3) - t * K;
-            sub_blk = t % nsub_blk;
-            chunk = (t / nsub_blk) * 8 + xcd;
-        } else {
-            chunk = b % n_chunks;
-            k = (b / n_chunks) % K;
-            sub_blk = b / (n_chunks * K);
-        }
-    }
+    // 1-D grid over (row chunk, offset, channel sub-block), XCD-ordered: wg_block
+    int chunk, k;
+    const int sub_blk = wg_block<true>(xcd_chunks, K, chunk, k);
     const int sub = COOP ? wv : sub_blk;
     const int m0 = (sub / nsub_n) * MTB, n0 = (sub % nsub_n) * NTB;
     const int row_begin = chunk * rows_per_chunk;
@@ -720,49 +793,13 @@ wgrad_kernel(const float* __restrict__ in, int n_in, int cin, const float* __res
         }
     };
 
-    int qn = 0;  // wave-uniform queue length (< 16 between batches)
-    // the neighbour ids of the NEXT 64 rows are requested before this batch's rounds run, so their latency is covered by those rounds
-    constexpr int BSTEP = COOP ? 64 : SC_BLOCK;
-    const int base0 = row_begin + (COOP ? 0 : wv * 64);
-    int iv_next = nbr[(size_t)k * n_out + min(base0 + lane, n_out - 1)];  // clamped, unconditional
-    for (int base = base0; base < row_end; base += BSTEP) {
-        const int o = base + lane;
-        const int iv = iv_next;
-        iv_next = nbr[(size_t)k * n_out + min(o + BSTEP, n_out - 1)];
-        const int i = o < row_end ? iv : -1;
-        const unsigned long long vote = __ballot(i >= 0);
-        if (vote == 0) continue;
-        if (i >= 0) {
-            const int pos = qn + __popcll(vote & ((1ull << lane) - 1));
-            qi[pos] = (int)((unsigned)i * row_a);
-            qo[pos] = (int)((unsigned)o * row_b);
-        }
-        qn += __popcll(vote);
-        __builtin_amdgcn_wave_barrier();
-        int done = 0;
-        while (qn - done >= 16) {
-            round16(done, qn, std::bool_constant<!COOP>{});     // (the cooperative 128 x 128 kernel measured 8 % slower without the per-step test)
-            done += 16;
-        }
-        const int left = qn - done;
-        if (done > 0 && left > 0) {  // move the tail (< 16 entries) to the front of the queue
-            int ti = 0, to = 0;
-            if (lane < left) {
-                ti = qi[done + lane];
-                to = qo[done + lane];
-            }
-            __builtin_amdgcn_wave_barrier();
-            if (lane < left) {
-                qi[lane] = ti;
-                qo[lane] = to;
-            }
-        }
-        qn = left;
-        __builtin_amdgcn_wave_barrier();
-    }
-    if (qn > 0) round16(0, qn, std::false_type{});
+    // the 4 waves take alternate 64-row batches of the chunk (COOP: every wave walks them all); full rounds carry no per-step test
+    // except in the cooperative 128 x 128 kernel, which measured 8 % slower without it
+    wg_pair_walk<16>(qi, qo, row_begin + (COOP ? 0 : wv * 64), row_end, COOP ? 64 : SC_BLOCK, nbr + (size_t)k * n_out, n_out, row_a, row_b,
+                     lane, std::bool_constant<!COOP>{}, round16);
 
-    // fold the 4 waves of the block in fixed order 0+1+2+3
+    // fold the 4 waves of the block in fixed order 0+1+2+3 (written out here and in wgrad_split_kernel: as a shared helper the 8 x 8-tile forms
+    // of this kernel, which spill, came out with other scratch sizes)
     for (int src = 1; !COOP && src < SC_BLOCK / 64; ++src) {
         if (wv == src) {
 #pragma unroll
@@ -784,18 +821,7 @@ wgrad_kernel(const float* __restrict__ in, int n_in, int cin, const float* __res
         __syncthreads();
     }
     if (!COOP && wv != 0) return;
-    // D: col = lane&15 -> cout tile column, row = 4*(lane>>4)+reg -> cin tile row
-    float* dst = slab + (size_t)chunk * cout * K * cin;
-#pragma unroll
-    for (int m = 0; m < MTB; ++m)
-#pragma unroll
-        for (int n = 0; n < NTB; ++n)
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const int ci = MT * (4 * g + reg) + m0 + m;
-                const int co = NT * ii + n0 + n;
-                if (ci < cin && co < cout) dst[((size_t)co * K + k) * cin + ci] = acc[m][n][reg];
-            }
+    wg_store_slab<true>(acc, slab, chunk, k, K, MT, NT, m0, n0, cin, cout, ii, g);
 }
 
 __global__ void __launch_bounds__(SC_BLOCK)

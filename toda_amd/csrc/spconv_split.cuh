@@ -19,7 +19,7 @@
 //     split in registers (5.5 vector instructions per value) - the vector pipe issues beside the matrix pipe of the other waves of the SIMD;
 //   * the rows of offset k + 1 are requested before the matrix work of offset k (one offset of look-ahead per wave) and land under it.
 // MFMA operand maps (cdna_hip_programming.md section 3): A[i = lane & 15][k = 8 (lane >> 4) + j], B[k = 8 (lane >> 4) + j][lane & 15],
-// D: col = lane & 15, row = 4 (lane >> 4) + reg (the map of the fp32 instruction: the epilogue is the one of gather_gemm_lds_kernel).
+// D: col = lane & 15, row = 4 (lane >> 4) + reg (the map of the fp32 instruction: the epilogue is gg_moments and gg_store_rows of spconv.hip).
 // k-permutation: lane (r, g) contracts element j of chunk kc over the gathered channel 32 kc + 16 (j >> 2) + 4 g + (j & 3): its two
 // 16-byte loads per chunk are the pieces 4 g .. 4 g + 3 of the 64-byte segments 2 kc and 2 kc + 1 of its row, so ONE load instruction
 // of the wave reads 16 rows x one whole 64-byte segment (a lane reading 32 KC contiguous bytes makes every instruction touch all
@@ -67,6 +67,25 @@ __device__ __forceinline__ void sp_split8(const f32x4& v0, const f32x4& v1, u32x
         const float l0 = r0 - sp_trunc(r0), l1 = r1 - sp_trunc(r1);
         l[p] = sp_pack_hi(l0, l1);
     }
+}
+// The six cross terms of one (N tile, 32-channel chunk), smallest first, into column n of the RT row tiles' accumulators.
+// XOR_ONLY (SP_ABLATE & 2, measurement builds): no matrix instructions, the operands are only kept alive.
+template <bool XOR_ONLY, int RT, int NT>
+__device__ __forceinline__ void sp_six_terms(f32x4 (&acc)[RT][NT], int n, const u32x4 (&ah)[RT], const u32x4 (&am)[RT], const u32x4 (&al)[RT],
+                                             const bf16x8& bh, const bf16x8& bm, const bf16x8& bl) {
+    auto term = [&](const u32x4 (&a)[RT], const bf16x8& b) {
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) {
+            if constexpr (XOR_ONLY) acc[rt][n][0] += __builtin_bit_cast(float, a[rt][0] ^ __builtin_bit_cast(u32x4, b)[0]);
+            else acc[rt][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a[rt]), b, acc[rt][n], 0, 0, 0);
+        }
+    };
+    term(al, bh);
+    term(ah, bl);
+    term(am, bm);
+    term(am, bh);
+    term(ah, bm);
+    term(ah, bh);
 }
 __device__ __forceinline__ unsigned short sp_plane_of(float v, int plane) {
     const float h = sp_trunc(v), r = v - h, m = sp_trunc(r), l = r - m;
@@ -145,21 +164,10 @@ gg_split_kernel(const float* __restrict__ in, int n_in, const u32x4* __restrict_
     const int row0 = wave * (16 * RT);
 
     f32x4 acc[RT][NT];
-#pragma unroll
-    for (int n = 0; n < NT; ++n) {
-        float b = 0.0f;
-        if (bias && NT * r + n < cp) b = bias[NT * r + n];
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) acc[rt][n] = f32x4{b, b, b, b};
-    }
-    const __amdgpu_buffer_rsrc_t in_rsrc = table_rsrc(in, (unsigned)n_in * (unsigned)CG * 4u);
     int rows[RT];
-    bool live[RT];
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-        live[rt] = row0 + rt * 16 + r < n_out;       // rows past the end read the ids of the last row and are never stored
-        rows[rt] = live[rt] ? (order ? order[row0 + rt * 16 + r] : row0 + rt * 16 + r) : n_out - 1;
-    }
+    bool live[RT];      // unused here: rows past the end read the ids of the last row and are never stored
+    gg_prologue<RT, NT>(bias, cp, row0, n_out, order, r, acc, rows, live);      // its order[] loads are the kernel's oldest vector-memory instructions
+    const __amdgpu_buffer_rsrc_t in_rsrc = table_rsrc(in, (unsigned)n_in * (unsigned)CG * 4u);
     // Data gradient of a strided convolution over class-sorted rows (GatherClasses, spconv.hip): when all rows of the WORKGROUP share one
     // residue class it walks only that class's offset list (<= 8 of 27, ascending: the same sums in the same order); the barriers
     // are the workgroup's, so one wave of another class sends the whole workgroup over all K offsets.
@@ -194,22 +202,16 @@ gg_split_kernel(const float* __restrict__ in, int n_in, const u32x4* __restrict_
         }
     };
     // rows of stage `part` of an offset: the lane's 16 bytes of the 64-byte segments 2 part and 2 part + 1
-    auto gather = [&](const int (&src)[RT], int part, bool valid, f32x4 (&raw)[RT][2]) {      // valid (wave-uniform): the offset exists
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) {
-            const bool ok = src[rt] >= 0 && valid;
-            const unsigned base = (unsigned)src[rt] * (unsigned)(CG * 4) + (unsigned)(16 * g) + 128u * (unsigned)part;
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-                raw[rt][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, ok ? base + 64u * i : OOB, 0, 0));
-        }
-    };
-    auto gather_rt = [&](const int (&src)[RT], int part, bool valid, f32x4 (&raw)[RT][2], int rt) {
+    auto gather_rt = [&](const int (&src)[RT], int part, bool valid, f32x4 (&raw)[RT][2], int rt) {      // valid (wave-uniform): the offset exists
         const bool ok = src[rt] >= 0 && valid;
         const unsigned base = (unsigned)src[rt] * (unsigned)(CG * 4) + (unsigned)(16 * g) + 128u * (unsigned)part;
 #pragma unroll
         for (int i = 0; i < 2; ++i)
             raw[rt][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, ok ? base + 64u * i : OOB, 0, 0));
+    };
+    auto gather = [&](const int (&src)[RT], int part, bool valid, f32x4 (&raw)[RT][2]) {
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) gather_rt(src, part, valid, raw, rt);
     };
     auto stage = [&](int st, int buf) {       // the slice of stage st = j KC + part: global -> LDS, 1 KiB per wave-instruction, no registers
         const int sc = st < KE * KC ? st : KE * KC - 1;
@@ -286,16 +288,7 @@ gg_split_kernel(const float* __restrict__ in, int n_in, const u32x4* __restrict_
 #pragma unroll
                         for (int p = 0; p < PIECES; ++p)
                             if (p * NT / PIECES == n) piece(p);
-#define SP_TERM(AA, BB)                                                                                                              \
-    _Pragma("unroll") for (int rt = 0; rt < RT; ++rt)                                                                                \
-        acc[rt][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, AA[rt]), BB, acc[rt][n], 0, 0, 0)
-                        SP_TERM(al, bh);
-                        SP_TERM(ah, bl);
-                        SP_TERM(am, bm);
-                        SP_TERM(am, bh);
-                        SP_TERM(ah, bm);
-                        SP_TERM(ah, bh);
-#undef SP_TERM
+                        sp_six_terms<false>(acc, n, ah, am, al, bh, bm, bl);
                     }
                 } else {
 #pragma unroll
@@ -327,22 +320,7 @@ gg_split_kernel(const float* __restrict__ in, int n_in, const u32x4* __restrict_
                 for (int n = 0; n < NT; ++n) {
                     const bf16x8 bh = __builtin_bit_cast(bf16x8, wb[(n * 3 + 0) * 64]), bm = __builtin_bit_cast(bf16x8, wb[(n * 3 + 1) * 64]),
                                  bl = __builtin_bit_cast(bf16x8, wb[(n * 3 + 2) * 64]);
-#if SP_ABLATE & 2
-#define SP_TERM(AA, BB)                                                                                                              \
-    _Pragma("unroll") for (int rt = 0; rt < RT; ++rt)                                                                                \
-        acc[rt][n][0] += __builtin_bit_cast(float, AA[rt][0] ^ __builtin_bit_cast(u32x4, BB)[0])
-#else
-#define SP_TERM(AA, BB)                                                                                                              \
-    _Pragma("unroll") for (int rt = 0; rt < RT; ++rt)                                                                                \
-        acc[rt][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, AA[rt]), BB, acc[rt][n], 0, 0, 0)
-#endif
-                    SP_TERM(al, bh);
-                    SP_TERM(ah, bl);
-                    SP_TERM(am, bm);
-                    SP_TERM(am, bh);
-                    SP_TERM(ah, bm);
-                    SP_TERM(ah, bh);
-#undef SP_TERM
+                    sp_six_terms<(SP_ABLATE & 2) != 0>(acc, n, ah, am, al, bh, bm, bl);
                 }
             }
             }
@@ -378,65 +356,10 @@ gg_split_kernel(const float* __restrict__ in, int n_in, const u32x4* __restrict_
         stats = nullptr;
     }
 #endif
-    // BatchNorm statistics of the layer's output from the accumulators - as gather_gemm_lds_kernel (same scratch layout and fold)
-    if (stats) {
-        float (*st_sh)[2][16 * NT] = reinterpret_cast<float (*)[2][16 * NT]>(wl);      // every wave is past its last slice read (barrier above)
-        float sm[NT], sq[NT];
-#pragma unroll
-        for (int n = 0; n < NT; ++n) {
-            sm[n] = sq[n] = 0.0f;
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-                for (int reg = 0; reg < 4; ++reg)
-                    if (row0 + rt * 16 + 4 * g + reg < n_out) {
-                        const float v = acc[rt][n][reg];
-                        sm[n] += v;
-                        sq[n] += v * v;
-                    }
-            sm[n] += __shfl_xor(sm[n], 16, 64);
-            sq[n] += __shfl_xor(sq[n], 16, 64);
-            sm[n] += __shfl_xor(sm[n], 32, 64);
-            sq[n] += __shfl_xor(sq[n], 32, 64);
-            if (g == 0) {
-                st_sh[wv][0][NT * r + n] = sm[n];
-                st_sh[wv][1][NT * r + n] = sq[n];
-            }
-        }
-        __syncthreads();
-        if ((int)threadIdx.x < 2 * cp) {
-            const int qq = threadIdx.x / cp, ch = threadIdx.x - qq * cp;
-            double a = 0.0;
-#pragma unroll
-            for (int w = 0; w < SC_BLOCK / 64; ++w) a += (double)st_sh[w][qq][ch];
-            stats[2 * cp + (size_t)(qq * cp + ch) * gridDim.x + blk] = a;
-        }
-    }
-
-    const bool full = cp == 16 * NT;
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-            const int pos = row0 + rt * 16 + 4 * g + reg;
-            const int row = __shfl(rows[rt], 4 * g + reg, 64);
-            if (pos >= n_out) continue;
-            float* dst = out + (size_t)row * cp + NT * r;
-            if (full) {
-                if constexpr (NT == 2) {
-                    *reinterpret_cast<float2*>(dst) = make_float2(acc[rt][0][reg], acc[rt][1][reg]);
-                } else {
-#pragma unroll
-                    for (int n = 0; n < NT; n += 4)
-                        *reinterpret_cast<f32x4*>(dst + n) = f32x4{acc[rt][n][reg], acc[rt][n + 1][reg], acc[rt][n + 2][reg], acc[rt][n + 3][reg]};
-                }
-            } else {
-#pragma unroll
-                for (int n = 0; n < NT; ++n)
-                    if (NT * r + n < cp) dst[n] = acc[rt][n][reg];
-            }
-        }
-    }
+    // BatchNorm statistics of the layer's output from the accumulators (gg_moments, spconv.hip); the scratch is the weight buffer: every
+    // wave is past its last slice read (barrier above)
+    if (stats) gg_moments<NT, RT, SC_BLOCK / 64>(reinterpret_cast<float (*)[2][16 * NT]>(wl), wv, blk, acc, row0, n_out, cp, stats, r, g);
+    gg_store_rows<RT, NT>(acc, rows, row0, n_out, cp, out, r, g);
 }
 
 // ---- weight gradient on the split path -----------------------------------------------------------------------------------------------
@@ -473,19 +396,8 @@ wgrad_split_kernel(const float* __restrict__ in, int n_in, const float* __restri
     __shared__ int q_in[SC_BLOCK / 64][QCAP], q_out[SC_BLOCK / 64][QCAP];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int ii = lane & 15, g = lane >> 4;
-    const int n_chunks = xcd_chunks < 0 ? -xcd_chunks : xcd_chunks;
     int chunk, k;
-    {
-        const int b = blockIdx.x;
-        if (xcd_chunks > 0) {      // the K offset-blocks of a chunk side by side on ONE XCD (see wgrad_kernel)
-            const int xcd = b & 7, t = (b >> 3) / K;
-            k = (b >> 3) - t * K;
-            chunk = t * 8 + xcd;
-        } else {
-            chunk = b % n_chunks;
-            k = b / n_chunks;
-        }
-    }
+    wg_block<false>(xcd_chunks, K, chunk, k);      // the K offset-blocks of a chunk side by side on ONE XCD
     const int row_begin = chunk * rows_per_chunk;
     if (row_begin >= n_out) return;      // a padding chunk of the XCD-ordered grid (whole block, before any barrier)
     const int row_end = min(n_out, row_begin + rows_per_chunk);
@@ -593,46 +505,8 @@ wgrad_split_kernel(const float* __restrict__ in, int n_in, const float* __restri
         }
     };
 
-    int qn = 0;  // wave-uniform queue length (< 32 between batches)
-    constexpr int BSTEP = TEAMS * 64;
-    const int base0 = row_begin + team * 64;
-    int iv_next = nbr[(size_t)k * n_out + min(base0 + lane, n_out - 1)];  // clamped, unconditional: the ids of the NEXT 64 rows are in flight
-    for (int base = base0; base < row_end; base += BSTEP) {               // under this batch's rounds
-        const int o = base + lane;
-        const int iv = iv_next;
-        iv_next = nbr[(size_t)k * n_out + min(o + BSTEP, n_out - 1)];
-        const int i = o < row_end ? iv : -1;
-        const unsigned long long vote = __ballot(i >= 0);
-        if (vote == 0) continue;
-        if (i >= 0) {
-            const int pos = qn + __popcll(vote & ((1ull << lane) - 1));
-            qi[pos] = (int)((unsigned)i * row_a);      // byte offsets of the rows
-            qo[pos] = (int)((unsigned)o * row_b);
-        }
-        qn += __popcll(vote);
-        __builtin_amdgcn_wave_barrier();
-        int done = 0;
-        while (qn - done >= 32) {
-            round32(done, qn, std::true_type{});
-            done += 32;
-        }
-        const int left = qn - done;
-        if (done > 0 && left > 0) {  // move the tail (< 32 entries) to the front of the queue
-            int ti = 0, to = 0;
-            if (lane < left) {
-                ti = qi[done + lane];
-                to = qo[done + lane];
-            }
-            __builtin_amdgcn_wave_barrier();
-            if (lane < left) {
-                qi[lane] = ti;
-                qo[lane] = to;
-            }
-        }
-        qn = left;
-        __builtin_amdgcn_wave_barrier();
-    }
-    if (qn > 0) round32(0, qn, std::false_type{});
+    // the teams of a quarter take alternate 64-row batches of the chunk
+    wg_pair_walk<32>(qi, qo, row_begin + team * 64, row_end, TEAMS * 64, nbr + (size_t)k * n_out, n_out, row_a, row_b, lane, std::true_type{}, round32);
 #if WGS_ACCS >= 2
 #pragma unroll
     for (int m = 0; m < MTB; ++m)
@@ -646,7 +520,7 @@ wgrad_split_kernel(const float* __restrict__ in, int n_in, const float* __restri
         }
 #endif
 
-    // fold the 4 waves of the block in fixed order 0+1+2+3, then the chunk's slab (as wgrad_kernel)
+    // fold the teams of each quarter in fixed order 0 + 1 + ... (the loop of wgrad_kernel over a quarter's slice of red), then the chunk's slab
     for (int src = 1; src < TEAMS; ++src) {
         float* const rq = red + qd * (MTB * NTB * 4 * 64);
         if (team == src) {
@@ -669,18 +543,7 @@ wgrad_split_kernel(const float* __restrict__ in, int n_in, const float* __restri
         __syncthreads();
     }
     if (team != 0) return;
-    // D: col = lane & 15 -> produced-channel tile column, row = 4 (lane >> 4) + reg -> gathered-channel tile row
-    float* dst = slab + (size_t)chunk * cout * K * cin;
-#pragma unroll
-    for (int m = 0; m < MTB; ++m)
-#pragma unroll
-        for (int n = 0; n < NTB; ++n)
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const int ci = MT * (4 * g + reg) + m0 + m;
-                const int co = NT * ii + n0 + n;
-                dst[((size_t)co * K + k) * cin + ci] = acc[m][n][reg];
-            }
+    wg_store_slab<false>(acc, slab, chunk, k, K, MT, NT, m0, n0, cin, cout, ii, g);
 }
 
 static inline bool wgrad_split_shape_ok(int cin, int cout) {
