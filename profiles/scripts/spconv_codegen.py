@@ -1,9 +1,13 @@
-"""Resources of the kernels of spconv.hip (spconv_split.cuh included), two builds paired by mangled name (no GPU).
+"""Resources of the kernels of one or more .hip files, two builds paired by mangled name (no GPU).
 
   python profiles/scripts/spconv_codegen.py A.txt B.txt
-      A.txt / B.txt = stderr of  hipcc <the Makefile's HIPFLAGS> -Rpass-analysis=kernel-resource-usage -c spconv.hip
-      -> registers, scratch, LDS bytes and occupancy per pair (profiles/spconv_shared_resources.txt)
+      A.txt / B.txt = stderr of  hipcc <the Makefile's HIPFLAGS> -Rpass-analysis=kernel-resource-usage -c FILE.hip, for one file
+      or several concatenated (the same files on both sides)
+      -> registers, scratch, LDS bytes and occupancy per pair
+         (spconv.hip: profiles/spconv_shared_resources.txt; rulebook.hip, dynvox.hip, voxel_pool.hip and the other includers of
+         scan.cuh: profiles/grid_index_shared_resources.txt)
 
+A kernel whose signature changed pairs by its unmangled name, and the line says so.
 Exit status 1 when the sets of names differ or a pair differs in scratch bytes, LDS bytes or occupancy."""
 import collections
 import re
@@ -31,6 +35,11 @@ def short(mangled):
 
 def main(pa, pb):
     a, b = resources(pa), resources(pb)
+    # a kernel whose signature changed on purpose: the one name left over on each side with the same unmangled name
+    only_a, only_b = {short(k): k for k in set(a) - set(b)}, {short(k): k for k in set(b) - set(a)}
+    for name in sorted(set(only_a) & set(only_b)):
+        print(f"{name}: paired by unmangled name ({only_a[name]} -> {only_b[name]})")
+        b[only_a[name]] = b.pop(only_b[name])
     if set(a) != set(b):
         print("kernel names differ:", sorted(set(a) ^ set(b)))
         return 1

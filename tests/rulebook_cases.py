@@ -179,7 +179,7 @@ def conv_reference(idx, batch, shape, ks, st, pd):
 
 # ---------------------------------------------------------------------------------------------- the grid index buffer
 class Layout:
-    """Byte layout of a grid-index buffer (gi_layout of rulebook.hip): {bits, rank of the word's first cell} pairs, the scan's
+    """Byte layout of a grid-index buffer (gi_layout of grid_index.cuh): {bits, rank of the word's first cell} pairs, the scan's
     partial sums, one total, one byte per lattice row (b, z, y); every region starts on a multiple of 256 bytes."""
 
     def __init__(self, batch, shape):
@@ -245,6 +245,7 @@ STRIDED_GEOMS = [
     ((1, 1, 9), (1, 1, 1), (0, 0, 4)),      # ks[2] > 8: the per-bit arm of the output-set kernel
     ((1, 1, 4), (1, 1, 4), (0, 0, 0)),      # 31 * 4 + 4 = 128 window bits: the widest x stride toda_gridindex_from_bitmap takes
     ((1, 1, 8), (1, 1, 2), (0, 0, 3)),      # the widest kernel of the shift-OR arm
+    ((3, 1, 1), (2, 1, 1), (0, 0, 0)),      # VoxelBackBone8x's last down-sampling layer: the <3, 1, 1> table kernels
 ]
 # (shape, batch)
 LATTICES = [
@@ -256,7 +257,7 @@ LATTICES = [
     ((4, 6, 64), 1),
 ]
 # the only combinations left out: an axis smaller than its kernel minus twice the padding leaves no output cell.  (geometry, lattice)
-EMPTY_OUTPUT = [(0, 3), (0, 4), (4, 3), (4, 4), (6, 3), (7, 3)]
+EMPTY_OUTPUT = [(0, 3), (0, 4), (4, 3), (4, 4), (6, 3), (7, 3), (8, 3), (8, 4)]
 STRIDED_CASES = [(g, l) for g in range(len(STRIDED_GEOMS)) for l in range(len(LATTICES)) if (g, l) not in EMPTY_OUTPUT]
 
 

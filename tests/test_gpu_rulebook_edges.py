@@ -170,7 +170,7 @@ def plan_conv(name, geom, order=1):
 # ================================================================================================ strided geometries
 @pytest.mark.parametrize("g,l", RC.STRIDED_CASES, ids=[RC.geom_id(g) + "-" + RC.lattice_id(l) for g, l in RC.STRIDED_CASES])
 def test_strided_geometry(g, l):
-    """Both builders on every geometry x lattice, except RC.EMPTY_OUTPUT: the six combinations whose output lattice has no cell
+    """Both builders on every geometry x lattice, except RC.EMPTY_OUTPUT: the combinations whose output lattice has no cell
     (an axis smaller than its kernel minus the padding), which test_rulebook_host.py proves to be exactly those."""
     geom = RC.STRIDED_GEOMS[g]
     lazy_conv("lattice-%d" % l, geom, order=0)

@@ -16,6 +16,7 @@
 // Every reduction after that reads its segment in seg_pts order with one thread per (voxel, column): no atomics, the same
 // order on every run, bit-reproducible.  Integer atomics only (bitmap bits, LDS histograms); no float atomic in this file.
 // Byte-bound index work: ~70 B per point plus the bitmap (2 bits of words + prefixes per key-space cell, memset per call).
+#include "grid_index.cuh"
 #include "radix_sort.cuh"
 
 namespace toda {
@@ -56,10 +57,7 @@ dv_mark_kernel(const float* __restrict__ pts, int n, int width, DvGeom g, uint2*
     if (i >= n) return;
     const long long key = dv_key(pts + (size_t)i * width, g);
     keep_pos[i] = key >= 0;
-    if (key < 0) return;
-    const unsigned bit = 1u << (unsigned)(key & 31);
-    unsigned* word = &cells[key >> 5].x;
-    if (!(*word & bit)) atomicOr(word, bit);      // a hot cell: once its bit is visible the atomics stop
+    if (key >= 0) gi_set_bit(cells, key);      // a hot cell: once its bit is visible the atomics stop
 }
 
 __global__ void __launch_bounds__(DV_BLOCK)
@@ -71,8 +69,7 @@ dv_rank_kernel(const float* __restrict__ pts, int n, int width, DvGeom g, const 
     const long long key = dv_key(pts + (size_t)i * width, g);
     keep[i] = key >= 0;
     if (key < 0) return;
-    const uint2 c = cells[key >> 5];
-    const int v = (int)c.y + __popc(c.x & ((1u << (unsigned)(key & 31)) - 1u));
+    const int v = gi_rank(cells, key);      // (its bit is set: dv_mark saw the same key)
     const int r = keep_pos[i];
     rows[r] = i;
     inv[r] = v;

@@ -28,16 +28,17 @@ __device__ __forceinline__ int wave_inclusive_scan(int v) {
     return v;
 }
 
-// exclusive prefix of v within a 256-thread block; *block_total = block sum
+// exclusive prefix of v within a block of BLOCK threads; *block_total = block sum
+template <int BLOCK = SCAN_BLOCK>
 __device__ __forceinline__ int block_exclusive_scan(int v, int* block_total) {
-    __shared__ int wsum[SCAN_BLOCK / 64];
+    __shared__ int wsum[BLOCK / 64];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     int inc = wave_inclusive_scan(v);
     if (lane == 63) wsum[w] = inc;
     __syncthreads();
     int base = 0, tot = 0;
 #pragma unroll
-    for (int i = 0; i < SCAN_BLOCK / 64; ++i) {
+    for (int i = 0; i < BLOCK / 64; ++i) {
         int s = wsum[i];
         if (i < w) base += s;
         tot += s;

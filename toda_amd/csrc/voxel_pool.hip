@@ -19,6 +19,7 @@
 // per-workgroup fp64 partials folded in a fixed order (pool_common.cuh).  No float atomics: every result is bit-reproducible.
 // The table (toda_voxel_pool_table, the name kept for ABI stability; per row its (m, s) entries ascending: integer counts, a scan
 // and the stable sort of radix_sort.cuh) also serves the SA gather's d P and the BEV interpolation's d map (pointnet2_stack.hip).
+#include "grid_index.cuh"
 #include "pool_common.cuh"
 #include "radix_sort.cuh"
 
@@ -33,16 +34,8 @@ constexpr int VM_BLOCKS = 256;         // moment partials (fixed: the fold order
 constexpr int VB_LANES = 4;            // row lanes per d a / d b workgroup (x 64 channels)
 constexpr int VB_BLOCKS = 256;
 
-// grid-index layout of rulebook.hip: {32 occupancy bits, popcount of all earlier words} per word, at offset 0 of the buffer
-__device__ __forceinline__ int vq_rank(const uint2* __restrict__ cells, long long lin) {
-    const uint2 c = cells[lin >> 5];
-    const unsigned bit = 1u << (lin & 31);
-    if (!(c.x & bit)) return -1;
-    return (int)c.y + __popc(c.x & (bit - 1));
-}
-
 struct VqGeom {
-    int B, Z, Y, X;
+    GridDims grid;
     int rz, ry, rx;
     int nsample;
     float radius2;
@@ -58,18 +51,17 @@ voxel_query_kernel(const float* __restrict__ new_xyz, const int4* __restrict__ n
     const float nx = new_xyz[(size_t)m * 3 + 0], ny = new_xyz[(size_t)m * 3 + 1], nz = new_xyz[(size_t)m * 3 + 2];
     int* out = idx + (size_t)m * g.nsample;
     int cnt = 0;
-    if ((unsigned)c.x < (unsigned)g.B) {
+    if ((unsigned)c.x < (unsigned)g.grid.B) {
         for (int dz = -g.rz; dz <= g.rz && cnt < g.nsample; ++dz) {
             const int z = c.y + dz;
-            if (z < 0 || z >= g.Z) continue;
+            if (z < 0 || z >= g.grid.D) continue;
             for (int dy = -g.ry; dy <= g.ry && cnt < g.nsample; ++dy) {
                 const int y = c.z + dy;
-                if (y < 0 || y >= g.Y) continue;
+                if (y < 0 || y >= g.grid.H) continue;
                 for (int dx = -g.rx; dx <= g.rx && cnt < g.nsample; ++dx) {
                     const int x = c.w + dx;
-                    if (x < 0 || x >= g.X) continue;
-                    const long long lin = (((long long)c.x * g.Z + z) * g.Y + y) * g.X + x;
-                    int row = vq_rank(cells, lin);
+                    if (x < 0 || x >= g.grid.W) continue;
+                    int row = gi_rank(cells, lin_index(c.x, z, y, x, g.grid));
                     if (row < 0) continue;
                     if (rowof) row = rowof[row];
                     if ((unsigned)row >= (unsigned)N) continue;
@@ -276,18 +268,18 @@ extern "C" int toda_voxel_query(const float* new_xyz, const int32_t* new_coords,
     TODA_CHECK_ARG((long long)M * nsample < (1LL << 31), "voxel_query: M x nsample too large");
     if (M == 0) return TODA_OK;
     TODA_CHECK_ARG(new_xyz && new_coords && gi && idx && empty && (N == 0 || xyz), "voxel_query: null pointer");
+    GiView v;
+    int rc = gi_view("voxel_query", gi, batch, shape_host, &v);
+    if (rc) return rc;
     VqGeom g;
-    g.B = batch;
-    g.Z = shape_host[0];
-    g.Y = shape_host[1];
-    g.X = shape_host[2];
+    g.grid = v.dims;
     g.rz = ranges_host[0];
     g.ry = ranges_host[1];
     g.rx = ranges_host[2];
     g.nsample = nsample;
     g.radius2 = radius * radius;        // fp32, as the reference's kernel argument
     hipLaunchKernelGGL(voxel_query_kernel, dim3(cdiv(M, VQ_BLOCK)), dim3(VQ_BLOCK), 0, (hipStream_t)stream, new_xyz,
-                       (const int4*)new_coords, M, xyz, N, (const uint2*)gi, (const int*)rowof, g, (int*)idx, empty);
+                       (const int4*)new_coords, M, xyz, N, (const uint2*)v.cells, (const int*)rowof, g, (int*)idx, empty);
     TODA_LAUNCH_CHECK();
     return TODA_OK;
 }
