@@ -15,7 +15,7 @@ from oracle import oracle as O
 pytestmark = pytest.mark.gpu
 
 N_OUT = [1, 16, 17, 33, 64, 65, 257]
-NATIVE = [(5, 16), (16, 16), (64, 32), (32, 64), (64, 64), (128, 64), (128, 128)]
+NATIVE = [(5, 16), (16, 16), (64, 32), (32, 64), (64, 64), (128, 64), (64, 128), (128, 128)]
 SPLIT = [(32, 32), (64, 64), (32, 128), (128, 128)]
 ROUTES = [("native", ci, co) for ci, co in NATIVE] + [("split", ci, co) for ci, co in SPLIT]
 SHAPE, BATCH = [3, 10, 10], 1

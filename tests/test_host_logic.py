@@ -327,3 +327,25 @@ def test_consistency_loss_ignores_inf_and_nan_in_unselected_candidate_rows():
     plain = get_consistency_loss([{"pred_boxes": a[va]}], [{"pred_boxes": o[vo]}])
     for c, p in zip(clean, plain):
         assert abs(float(c) - float(p)) < 1e-6
+
+
+def test_retired_knobs_raise_instead_of_being_ignored(monkeypatch):
+    """Every retired environment knob (the round-5 kernel families and the A/B switches retired after them): set, it makes
+    ops._refuse_retired_knobs raise with its name; "0" or unset, it does not."""
+    from toda_amd import ops
+
+    names = ops.RETIRED_KNOBS
+    assert len(names) == len(set(names)) == 30
+    assert {"TODA_GG_LINE", "TODA_HALO", "TODA_WINO_WGRAD"} <= set(names)      # the 13 of round 5 are still refused, with the 17 switches
+    for name in names:
+        monkeypatch.delenv(name, raising=False)
+    ops._refuse_retired_knobs()
+    for name in names:
+        monkeypatch.setenv(name, "1")
+        with pytest.raises(RuntimeError, match=rf"\b{name}\b"):
+            ops._refuse_retired_knobs()
+        monkeypatch.setenv(name, "0")
+        ops._refuse_retired_knobs()
+        monkeypatch.delenv(name)
+        ops._refuse_retired_knobs()
+

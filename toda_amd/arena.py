@@ -12,7 +12,7 @@ Here a prepared batch owns a SLOT: a few large chunks carved by bump allocation 
 host round trip) plus named persistent buffers whose contents carry an invariant from one use to the next (the voxel
 level's bitmap is all zero, the voxeliser's hash table is empty).  Slots rotate; the only synchronisation is one event per
 slot: recorded on the training stream when the step that consumed the slot has been enqueued, queried on the host by the
-pipeline's worker thread (or, host_wait=False, waited for by the side stream) before the slot is written again.  No
+pipeline's worker thread before the slot is written again.  No
 allocator traffic in steady state, no record_stream."""
 import threading
 
@@ -20,21 +20,8 @@ import torch
 
 _TLS = threading.local()
 CHUNK_BYTES = 512 << 20
-# How a pipeline's worker thread waits for an event on the host.  Blocking events + Event.synchronize(): the thread sleeps inside the
-# runtime with the interpreter lock RELEASED.  The round-4 first form polled Event.query() every 50 us - 20,000 lock hand-overs a second
-# taken from the thread that enqueues the step; harmless at 16 ms per step, but the forward-only loop (3.3 ms per step, 2.6 ms of them
-# host work) fell into alternating 3.3 / 4.3 ms steps on some boxes (profiles/r04_bench_c2_step_ms.txt).  TODA_PREFETCH_POLL=1: poll.
-import os as _os
-BLOCKING_EVENTS = _os.environ.get("TODA_PREFETCH_POLL", "0") != "1"
-
-
-def _host_wait(ev):
-    if BLOCKING_EVENTS:
-        ev.synchronize()
-        return
-    import time as _t
-    while not ev.query():
-        _t.sleep(5e-5)
+# A pipeline's worker thread waits for an event on the host through blocking events + Event.synchronize(): the thread sleeps inside
+# the runtime with the interpreter lock RELEASED, and takes nothing from the thread that enqueues the step.
 
 
 def current_slot():
@@ -123,13 +110,12 @@ class IndexArena:
     A slot is re-used when the event behind its last consumer has COMPLETED.  The check is made on the host (`Event.query`, by the
     pipeline's worker thread): with every slot in flight the worker sleeps until the oldest one is released and only then enqueues
     the next batch's index kernels, so the pipeline prepares one batch per GPU step, stays `slots - 2` steps ahead, and neither
-    stream ever waits for the other on the GPU (`host_wait=False`: `stream.wait_event` instead).  `slots < max_slots`: grow instead of
+    stream ever waits for the other on the GPU.  `slots < max_slots`: grow instead of
     waiting.  After the first batch the other slots are laid out like the first (`prewarm`), so nothing is allocated once the first
     preparation is over."""
 
-    def __init__(self, device, slots=4, max_slots=None, host_wait=True):
+    def __init__(self, device, slots=4, max_slots=None):
         self.device = torch.device(device)
-        self.host_wait = bool(host_wait)
         max_slots = slots if max_slots is None else max_slots
         self.slots = [ArenaSlot(device) for _ in range(max(2, int(slots)))]
         self.max_slots = max(int(max_slots), len(self.slots))
@@ -153,10 +139,9 @@ class IndexArena:
             if self._warm:
                 self._clone_layout(self.slots[0], pick)
         if pick is None:
-            # every slot is in flight and the arena is at its bound: wait for the OLDEST release - on the host (poll + sleep; this is the
-            # input pipeline's worker thread), so that the index kernels are enqueued only when they can run: the pipeline then prepares one
+            # every slot is in flight and the arena is at its bound: wait for the OLDEST release - on the host (this is the input
+            # pipeline's worker thread), so that the index kernels are enqueued only when they can run: the pipeline then prepares one
             # batch per GPU step and stays `max_slots - 2` steps ahead, with no queue-to-queue dependency on the GPU
-            import time as _t
             cands = [sl for sl in self.slots if not sl.in_use and sl.free_event is not None] or [sl for sl in self.slots if not sl.in_use]
             if not cands:
                 raise RuntimeError(f"IndexArena: all {n} slots are held by batches that were never released (a consumer keeps more than "
@@ -164,10 +149,7 @@ class IndexArena:
             pick = cands[self.turn % len(cands)]
             self.turn = (self.turn + 1) % n
             if pick.free_event is not None:
-                if self.host_wait:
-                    _host_wait(pick.free_event)
-                else:
-                    stream.wait_event(pick.free_event)
+                pick.free_event.synchronize()
             self.waits += 1
         pick.in_use = True          # until release(): a slot that is being prepared or consumed has no event to be judged by
         pick.reset()
@@ -177,7 +159,7 @@ class IndexArena:
         """Everything that reads `slot` has been enqueued on `stream`."""
         ev = slot.free_event
         if ev is None:
-            ev = slot.free_event = torch.cuda.Event(blocking=BLOCKING_EVENTS)
+            ev = slot.free_event = torch.cuda.Event(blocking=True)
         ev.record(stream)
         slot.in_use = False
 

@@ -245,25 +245,16 @@ __device__ __forceinline__ void gg_moments(float (*st_sh)[2][16 * NT], int wv, i
     }
 }
 
-// Block id of a weight-gradient grid -> (row chunk, offset[, channel sub-block: SUB]).  The K offset-blocks of a chunk read the same
+// Block id of a weight-gradient grid -> (row chunk, offset).  The K offset-blocks of a chunk read the same
 // dout rows and neighbouring input rows: they are given consecutive slots of ONE XCD (workgroup ids are dealt round-robin over the 8
 // XCDs, so XCD x owns ids x, x + 8, ...) and run side by side out of that XCD's L2.  With the offset as the slow grid axis (round 1)
 // the blocks of a chunk were on one XCD too, but a whole grid pass apart in time: PMC 1.50 GB from HBM per launch of the 32 -> 32
-// layer at 682 k rows against 0.27 GB algorithmic.  xcd_chunks < 0 (TODA_WG_XCD=0): plain order.  The launch pads the chunk count to a multiple of 8.
-template <bool SUB>
-__device__ __forceinline__ int wg_block(int xcd_chunks, int K, int& chunk, int& k) {      // returns the sub-block (0 without SUB)
-    const int n_chunks = xcd_chunks < 0 ? -xcd_chunks : xcd_chunks;
-    const int nsub_blk = SUB ? (int)gridDim.x / (n_chunks * K) : 1;
+// layer at 682 k rows against 0.27 GB algorithmic.  The launch pads the chunk count to a multiple of 8: the grid is (padded chunks) x K.
+__device__ __forceinline__ void wg_block(int K, int& chunk, int& k) {
     const int b = blockIdx.x;
-    if (xcd_chunks > 0) {
-        const int xcd = b & 7, t = (b >> 3) / K;
-        k = (b >> 3) - t * K;
-        chunk = (t / nsub_blk) * 8 + xcd;
-        return t % nsub_blk;
-    }
-    chunk = b % n_chunks;
-    k = SUB ? (b / n_chunks) % K : b / n_chunks;
-    return SUB ? b / (n_chunks * K) : 0;
+    const int xcd = b & 7, t = (b >> 3) / K;
+    k = (b >> 3) - t * K;
+    chunk = t * 8 + xcd;
 }
 
 // The pair walk of a wave of a weight-gradient kernel over the rows base0, base0 + bstep, ... < row_end of one offset (nbr_k = its
@@ -608,8 +599,8 @@ gather_gemm_lds_kernel(const float* __restrict__ in, int n_in, int cg, const flo
     gg_store_rows<RT, NT>(acc, rows, row0, n_out, cp, out, r, g);
 }
 
-// wgrad: dW[co][k][ci] = sum_o in[nbr[k][o]][ci] * dout[o][co].  Grid (row chunk, offset, channel
-// sub-block).  The contraction runs over PAIRS, not rows: every wave reads 64 neighbour ids at a
+// wgrad: dW[co][k][ci] = sum_o in[nbr[k][o]][ci] * dout[o][co].  Grid (row chunk, offset).
+// The contraction runs over PAIRS, not rows: every wave reads 64 neighbour ids at a
 // time (one coalesced 256-byte load), compacts the valid (in,out) pairs into a small LDS queue
 // (ballot + prefix popcount) and feeds the MFMAs 16 pairs per round (4 per MFMA step, one per lane
 // group), so no matrix work is spent on rows without a neighbour and each round has 4 steps of
@@ -626,8 +617,7 @@ typedef float f32x2w __attribute__((ext_vector_type(2)));
 template <int MTB, int NTB, bool COOP = false, bool EXACT = false>
 __global__ void __launch_bounds__(SC_BLOCK, (MTB * NTB <= 16) ? WG_WAVES : 1)
 wgrad_kernel(const float* __restrict__ in, int n_in, int cin, const float* __restrict__ dout, int cout,
-             const int* __restrict__ nbr, int n_out, int K, int rows_per_chunk, int MT, int NT, int nsub_n,
-             float* __restrict__ slab, int xcd_chunks) {
+             const int* __restrict__ nbr, int n_out, int K, int rows_per_chunk, int MT, int NT, float* __restrict__ slab) {
     constexpr int QCAP = 64 + 16;
     // a side of 16 or 32 channels (one or two tiles = the whole side: the launch gives blocks of fewer than four tiles only then) is staged
     constexpr bool STAGE_A = EXACT && !COOP && MTB < 4, STAGE_B = EXACT && !COOP && NTB < 4;
@@ -636,11 +626,10 @@ wgrad_kernel(const float* __restrict__ in, int n_in, int cin, const float* __res
     __shared__ int q_in[SC_BLOCK / 64][QCAP], q_out[SC_BLOCK / 64][QCAP];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int ii = lane & 15, g = lane >> 4;
-    // 1-D grid over (row chunk, offset, channel sub-block), XCD-ordered: wg_block
+    // 1-D grid over (row chunk, offset), XCD-ordered: wg_block
     int chunk, k;
-    const int sub_blk = wg_block<true>(xcd_chunks, K, chunk, k);
-    const int sub = COOP ? wv : sub_blk;
-    const int m0 = (sub / nsub_n) * MTB, n0 = (sub % nsub_n) * NTB;
+    wg_block(K, chunk, k);
+    const int m0 = COOP ? (wv / 2) * MTB : 0, n0 = COOP ? (wv % 2) * NTB : 0;      // COOP: the wave's quarter
     const int row_begin = chunk * rows_per_chunk;
     if (row_begin >= n_out) return;      // a padding chunk of the XCD-ordered grid (whole block, before any barrier)
     const int row_end = min(n_out, row_begin + rows_per_chunk);
@@ -798,8 +787,8 @@ wgrad_kernel(const float* __restrict__ in, int n_in, int cin, const float* __res
     wg_pair_walk<16>(qi, qo, row_begin + (COOP ? 0 : wv * 64), row_end, COOP ? 64 : SC_BLOCK, nbr + (size_t)k * n_out, n_out, row_a, row_b,
                      lane, std::bool_constant<!COOP>{}, round16);
 
-    // fold the 4 waves of the block in fixed order 0+1+2+3 (written out here and in wgrad_split_kernel: as a shared helper the 8 x 8-tile forms
-    // of this kernel, which spill, came out with other scratch sizes)
+    // fold the 4 waves of the block in fixed order 0+1+2+3 (written out here and in wgrad_split_kernel: as a shared helper the forms of this
+    // kernel that spill came out with other scratch sizes - seen on the 8 x 8-tile form, which is no longer instantiated)
     for (int src = 1; !COOP && src < SC_BLOCK / 64; ++src) {
         if (wv == src) {
 #pragma unroll
@@ -1108,16 +1097,15 @@ gather_gemm_compact_kernel(const float* __restrict__ in, int n_in, int cg, const
 }
 
 static void wgrad_plan(int n_out, int k_vol, int cin, int cout, int* chunks, int* rows_per_chunk) {
-    static const int env_chunks = getenv("TODA_WG_CHUNKS") ? atoi(getenv("TODA_WG_CHUNKS")) : 0;
-    int max_chunks = env_chunks > 0 ? env_chunks : ((tiles_pow2(cin) * tiles_pow2(cout) >= 16) ? 48 : 144);
-    if (env_chunks <= 0 && k_vol <= 9) max_chunks *= 2;
+    int max_chunks = (tiles_pow2(cin) * tiles_pow2(cout) >= 16) ? 48 : 144;
+    if (k_vol <= 9) max_chunks *= 2;
     int ch = k_vol <= 9 ? n_out / 1024 : n_out / 2048;
     if (ch < 1) ch = 1;
     if (ch > max_chunks) ch = max_chunks;
     // with the chunk's K offset-blocks side by side on one XCD (wgrad_kernel's grid order) the big levels take smaller chunks:
     // about 4 k rows each, at most 96 (64 -> 64 @ 389 k rows: 48 chunks 0.531 ms, 96 0.505, 192 0.509, 288 0.52; @ 117 k rows 48
     // chunks 0.187, 96 0.196)
-    if (env_chunks <= 0 && k_vol > 9 && max_chunks == 48 && n_out / 4096 > 48) ch = n_out / 4096 < 96 ? n_out / 4096 : 96;
+    if (k_vol > 9 && max_chunks == 48 && n_out / 4096 > 48) ch = n_out / 4096 < 96 ? n_out / 4096 : 96;
     if (ch >= 8) ch = (ch + 7) / 8 * 8;      // whole rounds of the 8 XCDs (55 chunks = 56 launched with one XCD a chunk short: 0.313 ms, 48: 0.304, 96: 0.296 on 64 -> 64 @ 227 k rows)
     int rpc = (n_out + ch - 1) / ch;
     rpc = (rpc + 15) / 16 * 16;
@@ -1437,9 +1425,7 @@ struct GatherRoute {
 static int gather_route(int c_gather, int c_produce, int n_out, bool stats, bool cls_sorted, GatherRoute* r) {
     const int Q = tiles_pow2(c_gather), NT = tiles_pow2(c_produce);
     const bool vec_ok = (c_gather & 3) == 0;
-    // weight staging: the LDS-shared slice when it measured faster (Q >= 2 and NT >= Q); TODA_GG_LDS = 0 never, 2 always
-    static const int env_lds_raw = getenv("TODA_GG_LDS") ? atoi(getenv("TODA_GG_LDS")) : 1;
-    const int env_lds = env_lds_raw == 2 ? 1 : (env_lds_raw == 1 ? (Q >= 2 && NT >= Q) : 0);
+    const bool lds_faster = Q >= 2 && NT >= Q;      // weight staging: the LDS-shared slice where it measured faster
     r->rt = 2, r->block = SC_BLOCK, r->vec = vec_ok;
     if (use_split(c_gather, c_produce)) {     // matrix path "split": wp holds the three-plane bf16 operand (spconv_split.cuh)
         TODA_CHECK_ARG(!(cls_sorted && stats), "gather_gemm (split path): no statistics on a class-sorted launch");
@@ -1448,7 +1434,7 @@ static int gather_route(int c_gather, int c_produce, int n_out, bool stats, bool
         // 128 -> 128: one 64 KiB slice shared by a 512-thread workgroup, 16 rows per wave (0.67 ms against 0.76 for two row tiles per
         // wave and 0.70 for register-only weights on 97.5k x 27 x 128 x 128)
         r->family = GatherRoute::LDS_128, r->rt = 1, r->block = 512;
-    } else if ((env_lds || stats) && !cls_sorted && vec_ok && Q * NT <= 32) {  // weight slice <= 32 KiB per buffer
+    } else if ((lds_faster || stats) && !cls_sorted && vec_ok && Q * NT <= 32) {  // weight slice <= 32 KiB per buffer
         r->family = GatherRoute::LDS, r->rt = NT < 8 ? 2 : 1;
     } else {
         // register-resident weights (gather_gemm_kernel): the narrow, the "more gathered than produced" and the class-sorted launches;
@@ -1695,55 +1681,38 @@ extern "C" int toda_spconv_wgrad(const float* in, int n_in, const float* dout, c
         return TODA_EWORKSPACE;
     }
     const int MT = tiles_pow2(cin), NT = tiles_pow2(cout);
-    static const int env_sub = getenv("TODA_WG_SUB") ? atoi(getenv("TODA_WG_SUB")) : 7;  // 128-channel sides take 8 tiles per block: 1.08 -> 0.76 ms on 97.5k x 27 x 128 x 128
-    static const int env_wg_xcd = getenv("TODA_WG_XCD") ? atoi(getenv("TODA_WG_XCD")) : 1;
-    const int chunks_launch = env_wg_xcd ? (chunks + 7) / 8 * 8 : chunks;      // padded to whole rounds of the 8 XCDs: blocks of the padding chunks leave at once
-    const int xcd_chunks = env_wg_xcd ? chunks_launch : -chunks;
+    const int chunks_launch = (chunks + 7) / 8 * 8;      // padded to whole rounds of the 8 XCDs (wg_block): blocks of the padding chunks leave at once
+    const int grid = chunks_launch * k_vol;
     const bool exact = cin == 16 * MT && cout == 16 * NT;
     float* slab = (float*)ws;
-
-    // the route: kernel family, tiles per block of each side, channel sub-blocks along cout, workgroups
-    enum { SPLIT, COOP, TILED } family;
-    int mtb = MT < 4 ? MT : 4, ntb = NT < 4 ? NT : 4, nsub_n = 1, grid = chunks_launch * k_vol;
-    if (matrix_path() == 1 && toda::wgrad_split_shape_ok(cin, cout)) {      // matrix path "split": spconv_split.cuh
-        family = SPLIT;
-    } else if (MT == 8 && NT == 8 && (env_sub & 4)) {   // cooperative quarters: 0.75 -> 0.68 ms on 97.5k x 27 x 128 x 128
-        family = COOP, nsub_n = 2;
-    } else {
-        family = TILED;
-        if (MT == 8 && (env_sub & 1)) mtb = 8;
-        if (NT == 8 && (env_sub & 2)) ntb = 8;
-        nsub_n = NT / ntb;
-        grid *= (MT / mtb) * nsub_n;
-    }
     auto split = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(SC_BLOCK), 0, s, in, n_in, dout, nbr, n_out, k_vol, rpc, slab, xcd_chunks);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(SC_BLOCK), 0, s, in, n_in, dout, nbr, n_out, k_vol, rpc, slab);
     };
     auto native = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(SC_BLOCK), 0, s, in, n_in, cin, dout, cout, nbr, n_out, k_vol, rpc, MT, NT, nsub_n, slab,
-                           xcd_chunks);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(SC_BLOCK), 0, s, in, n_in, cin, dout, cout, nbr, n_out, k_vol, rpc, MT, NT, slab);
     };
-    switch (family) {
-        case SPLIT:      // 32 / 64 channels a side: one block; 128: two 64-channel quarters along that side
-            if (cin == 128 && cout == 128) split(wgrad_split_kernel<4, 4, 2, 2>);
-            else if (cin == 64 && cout == 128) split(wgrad_split_kernel<4, 4, 1, 2>);
-            else if (cin == 128 && cout == 64) split(wgrad_split_kernel<4, 4, 2, 1>);
-            else if (cin == 32 && cout == 32) split(wgrad_split_kernel<2, 2>);
-            else if (cin == 32) split(wgrad_split_kernel<2, 4>);
-            else if (cout == 32) split(wgrad_split_kernel<4, 2>);
-            else split(wgrad_split_kernel<4, 4>);
-            break;
-        case COOP:
-            if (exact) native(wgrad_kernel<4, 4, true, true>);
-            else native(wgrad_kernel<4, 4, true>);
-            break;
-        case TILED:
-            with_tiles(mtb, ntb, [&](auto m, auto n) {
-                constexpr int MTB = decltype(m)::value, NTB = decltype(n)::value;
+    if (matrix_path() == 1 && toda::wgrad_split_shape_ok(cin, cout)) {      // matrix path "split": spconv_split.cuh
+        // 32 / 64 channels a side: one block; 128: two 64-channel quarters along that side
+        if (cin == 128 && cout == 128) split(wgrad_split_kernel<4, 4, 2, 2>);
+        else if (cin == 64 && cout == 128) split(wgrad_split_kernel<4, 4, 1, 2>);
+        else if (cin == 128 && cout == 64) split(wgrad_split_kernel<4, 4, 2, 1>);
+        else if (cin == 32 && cout == 32) split(wgrad_split_kernel<2, 2>);
+        else if (cin == 32) split(wgrad_split_kernel<2, 4>);
+        else if (cout == 32) split(wgrad_split_kernel<4, 2>);
+        else split(wgrad_split_kernel<4, 4>);
+    } else if (MT == 8 && NT == 8) {
+        // 128 x 128 as four cooperating 64 x 64 quarters, one per wave: 0.75 -> 0.68 ms on 97.5k x 27 x 128 x 128
+        if (exact) native(wgrad_kernel<4, 4, true, true>);
+        else native(wgrad_kernel<4, 4, true>);
+    } else {
+        // one block holds all tiles of both sides; a 128-channel side as 8 tiles (against two 4-tile blocks: 1.08 -> 0.76 ms on 97.5k x 27 x 128 x 128)
+        with_tiles(MT, NT, [&](auto m, auto n) {
+            constexpr int MTB = decltype(m)::value, NTB = decltype(n)::value;
+            if constexpr (MTB < 8 || NTB < 8) {      // (8 x 8 is the cooperative kernel's)
                 if (exact) native(wgrad_kernel<MTB, NTB, false, true>);
                 else native(wgrad_kernel<MTB, NTB>);
-            });
-            break;
+            }
+        });
     }
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(elems, SC_BLOCK)), dim3(SC_BLOCK), 0, s, slab, chunks, elems, dw);
     TODA_LAUNCH_CHECK();

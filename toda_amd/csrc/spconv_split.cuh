@@ -384,7 +384,7 @@ template <int MTB, int NTB, int QM = 1, int QN = 1>
 // 32 x 64 wants 175 registers: two waves per SIMD without spills (0.129 ms at spconv3 of C3) beat three with 13 spilled dwords (0.162)
 __global__ void __launch_bounds__(SC_BLOCK, (MTB * NTB <= 4) ? 4 : ((MTB == 4 && NTB == 2) ? 3 : 2))
 wgrad_split_kernel(const float* __restrict__ in, int n_in, const float* __restrict__ dout, const int* __restrict__ nbr, int n_out, int K,
-                   int rows_per_chunk, float* __restrict__ slab, int xcd_chunks) {
+                   int rows_per_chunk, float* __restrict__ slab) {
     static_assert((MTB == 2 || MTB == 4) && (NTB == 2 || NTB == 4), "32 or 64 channels a side");
     static_assert(QM * QN == 1 || (MTB == 4 && NTB == 4), "quarters are 64 x 64");
     static_assert(QM * QN == 1 || QM * QN == 2 || QM * QN == 4, "1, 2 or 4 quarters");
@@ -397,7 +397,7 @@ wgrad_split_kernel(const float* __restrict__ in, int n_in, const float* __restri
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int ii = lane & 15, g = lane >> 4;
     int chunk, k;
-    wg_block<false>(xcd_chunks, K, chunk, k);      // the K offset-blocks of a chunk side by side on ONE XCD
+    wg_block(K, chunk, k);      // the K offset-blocks of a chunk side by side on ONE XCD
     const int row_begin = chunk * rows_per_chunk;
     if (row_begin >= n_out) return;      // a padding chunk of the XCD-ordered grid (whole block, before any barrier)
     const int row_end = min(n_out, row_begin + rows_per_chunk);

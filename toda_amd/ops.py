@@ -438,7 +438,7 @@ class Rulebook:
         """(order, cls_sorted) of the data-gradient table of a strided convolution: its rows regrouped by the residue class of
         (coordinate + padding) mod stride, which fixes the 1..8 kernel offsets a row can have (toda_rulebook_class_order).
         None when not applicable."""
-        if (not CLASS_DGRAD or self.kind != "conv" or self.in_indices is None or self.k_vol > 27 or self.k_vol < 2
+        if (self.kind != "conv" or self.in_indices is None or self.k_vol > 27 or self.k_vol < 2
                 or self.n_in < CLASS_DGRAD_MIN_ROWS or any(int(v) not in (1, 2) for v in self.geom["stride"])):
             return None
         if self._class_order is None:
@@ -776,13 +776,21 @@ def gather_gemm(feat, wp, nbr, c_produce, bias=None, order=None):
     return out
 
 
+# What _refuse_retired_knobs refuses: kernel families that were measured and lost (round 5), then the A/B switches whose choice was
+# settled by measurement - the losing side is gone, the winner is the only path (profiles/EXPERIMENTS.md)
+RETIRED_KNOBS = ("TODA_GG_LINE", "TODA_HALO", "TODA_WG_TILE", "TODA_ROW_ORDER", "TODA_GG_WS", "TODA_GG_STAGE", "TODA_GG_WRES", "TODA_GG_LDS_PF",
+                 "TODA_GG_BLK512", "TODA_GG_RT", "TODA_SPLIT_BLK", "TODA_SPLIT_KCS", "TODA_WINO_WGRAD",
+                 "TODA_WGRAD_STREAM", "TODA_BN_FOLD_FINALIZE", "TODA_FUSE_BN_STATS", "TODA_GG_COMPACT", "TODA_CLASS_DGRAD", "TODA_BN_BWD_COLSUM",
+                 "TODA_GG_LDS", "TODA_WG_SUB", "TODA_WG_XCD", "TODA_WG_CHUNKS", "TODA_PREFETCH_PRIORITY", "TODA_PREFETCH_ARENA",
+                 "TODA_PREFETCH_STREAM_WAIT", "TODA_PREFETCH_HOST_WAIT", "TODA_PREFETCH_PHASE", "TODA_PREFETCH_POLL", "TODA_DENSE_CHANNELS_LAST")
+
+
 def _refuse_retired_knobs():
-    """Environment knobs of kernel families that were measured, lost and are no longer in the library (profiles/EXPERIMENTS.md), and of
-    the measurement-only ablation builds: asking for one of them is an error, not a silent no-op."""
-    retired = [k for k in ("TODA_GG_LINE", "TODA_HALO", "TODA_WG_TILE", "TODA_ROW_ORDER", "TODA_GG_WS", "TODA_GG_STAGE", "TODA_GG_WRES", "TODA_GG_LDS_PF",
-                           "TODA_GG_BLK512", "TODA_GG_RT", "TODA_SPLIT_BLK", "TODA_SPLIT_KCS", "TODA_WINO_WGRAD") if _os.environ.get(k, "0") not in ("0", "")]
+    """Environment knobs of kernel families and code paths that were measured, lost and are no longer there (profiles/EXPERIMENTS.md),
+    and of the measurement-only ablation builds: asking for one of them is an error, not a silent no-op."""
+    retired = [k for k in RETIRED_KNOBS if _os.environ.get(k, "0") not in ("0", "")]
     if retired:
-        raise RuntimeError(f"{', '.join(retired)}: these kernel variants were retired (profiles/EXPERIMENTS.md); unset the variable(s)")
+        raise RuntimeError(f"{', '.join(retired)}: these variants were retired (profiles/EXPERIMENTS.md); unset the variable(s)")
     ablate = [k for k in ("TODA_GG_ABLATE", "TODA_WINO_ABLATE", "TODA_WINO_WG_ABLATE") if _os.environ.get(k, "0") not in ("0", "")]
     if ablate and not _os.environ.get("TODA_HIP_LIB"):
         raise RuntimeError(f"{', '.join(ablate)} only act in a measurement build (-DTODA_ABLATE=1, loaded through TODA_HIP_LIB): the library "
@@ -794,7 +802,7 @@ _refuse_retired_knobs()
 
 # narrow K = 27 layers (conv_input, the 16-channel SubM level, the strided 16 -> 32 and its data gradient) by per-offset compaction:
 # measured on the C3 levels 5 -> 16 80 -> 42 us, 16 -> 16 70 -> 38, 16 -> 32 @ 682 k rows 141 -> 122, 32 -> 16 (dgrad) 69 -> 61
-COMPACT = _os.environ.get("TODA_GG_COMPACT", "1") == "1"
+COMPACT = True          # (tests switch it off to reach the packed kernels at these shapes)
 
 
 def _compact_route(c_gather, c_produce, nbr):
@@ -854,17 +862,7 @@ def wgrad(feat, dout, nbr, wshape):
 
 
 # data gradient of strided convolutions over residue-class-sorted rows (1..8 candidate offsets per row instead of 27)
-CLASS_DGRAD = _os.environ.get("TODA_CLASS_DGRAD", "1") == "1"
-CLASS_DGRAD_MIN_ROWS = int(_os.environ.get("TODA_CLASS_DGRAD_MIN_ROWS", "4096"))
-WGRAD_ON_SIDE_STREAM = _os.environ.get("TODA_WGRAD_STREAM", "0") == "1"  # measured: no gain (each kernel already fills the chip)
-_SIDE_STREAMS = {}
-
-
-def _side_stream(device):
-    key = (device.type, device.index)
-    if key not in _SIDE_STREAMS:
-        _SIDE_STREAMS[key] = torch.cuda.Stream(device=device)
-    return _SIDE_STREAMS[key]
+CLASS_DGRAD_MIN_ROWS = 4096
 
 
 class _SparseConv(torch.autograd.Function):
@@ -880,13 +878,10 @@ class _SparseConv(torch.autograd.Function):
             wp_fwd = pack_weight(weight, False, False)
         if wp_fwd is not None:
             _check_mm(wp_fwd)
-        sums, blocks = None, 0
         if compact and want_stats:
             out, sums, blocks = gather_gemm_compact(features, weight.contiguous(), rb.nbr_fwd, weight.shape[0], bias, stats=True)
-        elif want_stats and FOLD_IN_FINALIZE:
-            out, sums, blocks = gather_gemm_with_stats(features, wp_fwd, rb.nbr_fwd, weight.shape[0], bias, partials=True)
         elif want_stats:
-            out, sums = gather_gemm_with_stats(features, wp_fwd, rb.nbr_fwd, weight.shape[0], bias)
+            out, sums, blocks = gather_gemm_with_stats(features, wp_fwd, rb.nbr_fwd, weight.shape[0], bias, partials=True)
         elif compact:
             out = gather_gemm_compact(features, weight.contiguous(), rb.nbr_fwd, weight.shape[0], bias)
         else:
@@ -898,7 +893,7 @@ class _SparseConv(torch.autograd.Function):
         ctx.has_bias = bias is not None
         if want_stats:
             ctx.mark_non_differentiable(sums)
-            return out, sums, blocks       # blocks > 0: sums holds unfolded per-workgroup partials (toda_bn_finalize_partials)
+            return out, sums, blocks       # sums: unfolded partials of `blocks` workgroups (toda_bn_finalize_partials)
         return out
 
     @staticmethod
@@ -910,17 +905,6 @@ class _SparseConv(torch.autograd.Function):
         gout = gout.contiguous()
         gfeat = gw = gb = None
         need_d, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        side = _side_stream(gout.device) if (need_d and need_w and WGRAD_ON_SIDE_STREAM) else None
-        if side is not None:
-            # dgrad and wgrad only share their inputs: run wgrad on a second HIP stream so that the two
-            # MFMA-bound kernels (each ~60 % matrix-pipe utilisation on its own) fill each other's gaps
-            main = torch.cuda.current_stream(gout.device)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                gw = wgrad(features, gout, rb.nbr_fwd, tuple(weight.shape))
-            for t in (features, gout, rb.nbr_fwd):
-                t.record_stream(side)
-            need_w = False
         if need_d and _compact_route(gout.shape[1], weight.shape[-1], rb.nbr_bwd):
             gfeat = gather_gemm_compact(gout, weight.contiguous(), rb.nbr_bwd, weight.shape[-1], None, True, rb.flip_bwd)
         elif need_d:
@@ -937,28 +921,21 @@ class _SparseConv(torch.autograd.Function):
             gb = _take_colsum(gout)          # BatchNorm's backward has already summed its dx over the rows (toda_rows_bn_bwd_res_colsum)
             if gb is None:
                 gb = gout.sum(0)
-        if side is not None:
-            torch.cuda.current_stream(gout.device).wait_stream(side)
-            gw.record_stream(torch.cuda.current_stream(gout.device))
         return gfeat, gw, gb, None, None, None, None
-
-
-FUSE_BN_STATS = _os.environ.get("TODA_FUSE_BN_STATS", "1") == "1"
-FOLD_IN_FINALIZE = _os.environ.get("TODA_BN_FOLD_FINALIZE", "1") == "1"     # the fold of the epilogue's partial sums inside the finalise launch
 
 
 def sparse_conv(features, weight, bias, rulebook, packed_weight=None, want_stats=False, packed_dgrad=None):
     """want_stats: also return the BatchNorm moments of the output when the kernel's epilogue can take them
-    (returns (out, sums) with sums None when it cannot: empty tables, narrow channel pairs, mask-sorted row order)."""
+    (returns (out, sums) with sums the unfolded (partials, blocks) pair that bn_rows takes, or None when it cannot: empty tables,
+    unsupported channel pairs)."""
     if not want_stats:
         return _SparseConv.apply(features, weight, bias, rulebook, packed_weight, False, packed_dgrad)
-    narrow = FOLD_IN_FINALIZE and _compact_route(features.shape[1], weight.shape[0], rulebook.nbr_fwd)
-    ok = (FUSE_BN_STATS and (narrow or gather_gemm_stats_supported(weight.shape[-1], weight.shape[0])) and rulebook.nbr_fwd.shape[1] > 1
-          and features.shape[0] > 0)
+    narrow = _compact_route(features.shape[1], weight.shape[0], rulebook.nbr_fwd)
+    ok = (narrow or gather_gemm_stats_supported(weight.shape[-1], weight.shape[0])) and rulebook.nbr_fwd.shape[1] > 1 and features.shape[0] > 0
     if not ok:
         return _SparseConv.apply(features, weight, bias, rulebook, packed_weight, False, packed_dgrad), None
     out, sums, blocks = _SparseConv.apply(features, weight, bias, rulebook, packed_weight, True, packed_dgrad)
-    return out, ((sums, blocks) if blocks else sums)
+    return out, (sums, blocks)
 
 
 # ------------------------------------------------------------------------ sparse <-> dense
@@ -1042,7 +1019,7 @@ def rows_affine_act(x, scale, shift, residual=None, relu=True):
 # the gradient tensor, which autograd passes on untouched when the convolution's output has that one consumer.  The entry holds
 # the tensor itself, so its address cannot be re-used while the entry is alive; whatever is left over is dropped by the next forward.
 _DX_COLSUM = {}
-BN_BWD_COLSUM = _os.environ.get("TODA_BN_BWD_COLSUM", "1") == "1"
+BN_BWD_COLSUM = True    # (tests switch it off for their reference)
 
 
 def _take_colsum(gout):

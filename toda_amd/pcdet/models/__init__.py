@@ -116,10 +116,9 @@ class InputPrefetcher:
         # HIGH priority: the side stream's kernels are small (index building) and the host WAITS for them twice per batch; at
         # normal priority they queue behind the backward pass's chip-filling kernels, the host comes back from kick() only when
         # that pass is done and the GPU then idles while the next forward is being enqueued (r02 trace: 0.6-0.9 ms gaps at the
-        # step boundary).  TODA_PREFETCH_PRIORITY=0 restores the default priority.
+        # step boundary).
         import os
-        prio = int(os.environ.get("TODA_PREFETCH_PRIORITY", "-1"))
-        self.side = torch.cuda.Stream(device=device, priority=prio)
+        self.side = torch.cuda.Stream(device=device, priority=-1)
         # device tensors that exist already (resident clouds, an object database, the model's weights) were produced on the
         # caller's stream: the side stream waits for that stream ONCE, here.  Not in kick(): kick() runs right behind an enqueued
         # backward pass and must not wait for it - what a later batch reads is either uploaded on the side stream itself or
@@ -128,36 +127,14 @@ class InputPrefetcher:
         self.pending = None
         # Device memory of the prepared batches: arena slots (toda_amd.arena) instead of the caching allocator - what the side stream
         # produces is consumed on the caller's stream a step later, the worst case for a stream-aware allocator (round 3: hipMalloc
-        # calls inside steady-state steps).  A slot is re-used when its last consumer has finished (host-side event query by the worker;
-        # neither stream waits for the other on the GPU).  TODA_PREFETCH_ARENA=0 goes back to the allocator.
+        # calls inside steady-state steps).  A slot is re-used when its last consumer has finished (host-side event wait; neither
+        # stream waits for the other on the GPU).
         from ... import arena as _arena
         self._arena_mod = _arena
-        self.arena = None
-        if os.environ.get("TODA_PREFETCH_ARENA", "1") == "1":
-            n_slots = int(os.environ.get("TODA_PREFETCH_SLOTS", "2"))
-            self.arena = _arena.IndexArena(device, n_slots, int(os.environ.get("TODA_PREFETCH_MAX_SLOTS", n_slots)),
-                                           host_wait=os.environ.get("TODA_PREFETCH_STREAM_WAIT", "0") != "1")
+        n_slots = int(os.environ.get("TODA_PREFETCH_SLOTS", "2"))
+        self.arena = _arena.IndexArena(device, n_slots, int(os.environ.get("TODA_PREFETCH_MAX_SLOTS", n_slots)))
         self._in_use = None          # slot of the batch the caller is consuming
         self._poison = os.environ.get("TODA_PREFETCH_DEBUG_POISON", "0") == "1"
-        # (Round 4 measured WHERE in the step the index kernels run - start of the forward, behind the sparse forward, at the start of the
-        # dense or sparse backward - and whether the side stream waits for the training stream on the GPU or the worker waits on the host:
-        # 16.87-16.99 ms per step everywhere.  A batch's ~0.5 ms of index kernels costs ~0.4 ms wherever it lands: the training stream
-        # leaves no idle capacity to hide it in - without any input pipeline the step is 16.4 ms.  DESIGN.md section 5.)
-        self._host_wait = os.environ.get("TODA_PREFETCH_HOST_WAIT", "1") == "1" and os.environ.get("TODA_PREFETCH_THREAD", "1") == "1"
-        # Phase of the index kernels inside the consumer's step: with two slots a preparation starts when a step ends, i.e. it lands
-        # under the next step's sparse forward - on the C3 step right on the dominant 64 -> 64 gather-GEMMs (0.605 instead of 0.58 ms per
-        # launch).  The worker therefore also waits (on the host) until the training stream has passed the sparse backbone's forward of
-        # the step in flight: an event recorded by a forward hook on backbone_3d.  The index kernels then run beside the dense neck.
-        self._fwd_done = None
-        self._phase_hook = None
-        bb = getattr(net, "backbone_3d", None)
-        if os.environ.get("TODA_PREFETCH_PHASE", "1") == "1" and self.arena is not None and self._host_wait and bb is not None:
-            def _mark(_m, _a, _out):
-                if torch.is_grad_enabled():      # training steps only (the forward-only loops have no slack to wait in)
-                    ev = torch.cuda.Event(blocking=self._arena_mod.BLOCKING_EVENTS)
-                    ev.record()
-                    self._fwd_done = ev
-            self._phase_hook = bb.register_forward_hook(_mark)
         self._trace = [] if os.environ.get("TODA_PREFETCH_TRACE") else None      # (seconds per preparation, of which waiting for the counts)
         # The preparation runs on a worker thread (TODA_PREFETCH_THREAD=0: on the caller's), so its two host syncs and its ~150
         # launches overlap the caller's own enqueueing instead of following it: the forward-only workload is host-bound otherwise
@@ -168,6 +145,20 @@ class InputPrefetcher:
         if os.environ.get("TODA_PREFETCH_THREAD", "1") == "1":
             from concurrent.futures import ThreadPoolExecutor
             self.pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="toda-prefetch")
+        # Phase of the index kernels inside the consumer's step: with two slots a preparation starts when a step ends, i.e. it lands
+        # under the next step's sparse forward - on the C3 step right on the dominant 64 -> 64 gather-GEMMs (0.605 instead of 0.58 ms per
+        # launch).  The worker therefore also waits (on the host) until the training stream has passed the sparse backbone's forward of
+        # the step in flight: an event recorded by a forward hook on backbone_3d.  The index kernels then run beside the dense neck.
+        self._fwd_done = None
+        self._phase_hook = None
+        bb = getattr(net, "backbone_3d", None)
+        if self.pool is not None and bb is not None:
+            def _mark(_m, _a, _out):
+                if torch.is_grad_enabled():      # training steps only (the forward-only loops have no slack to wait in)
+                    ev = torch.cuda.Event(blocking=True)
+                    ev.record()
+                    self._fwd_done = ev
+            self._phase_hook = bb.register_forward_hook(_mark)
         if eager:
             self.kick()
 
@@ -189,10 +180,10 @@ class InputPrefetcher:
                 batch = next(self.it)        # inside the side-stream context: a source that mixes / collates on the device runs there too
             except StopIteration:
                 return None
-            slot = self.arena.acquire(self.side) if self.arena is not None else None      # (waits on the host for a free slot)
+            slot = self.arena.acquire(self.side)      # (waits on the host for a free slot)
             gate = self._fwd_done
-            if gate is not None and slot is not None:
-                self._arena_mod._host_wait(gate)
+            if gate is not None:
+                gate.synchronize()
             try:
                 with self._arena_mod.use_slot(slot):
                     if isinstance(batch, (tuple, list)):      # the (adversarial, original) pair of the stage-2 consistency step
@@ -202,18 +193,16 @@ class InputPrefetcher:
             except BaseException:
                 # the slot must not stay "in use" for good (with two slots the NEXT acquire would find none and hide this error);
                 # the caller sees the original exception from next()
-                if slot is not None:
-                    self.arena.abandon(slot)
+                self.arena.abandon(slot)
                 raise
-            if self.arena is not None:
-                self.arena.prewarm()         # once: the other slots get the first one's layout (no device allocation after the warm-up steps)
-            ev = torch.cuda.Event(blocking=self._arena_mod.BLOCKING_EVENTS)
+            self.arena.prewarm()         # once: the other slots get the first one's layout (no device allocation after the warm-up steps)
+            ev = torch.cuda.Event(blocking=True)
             ev.record(self.side)
-            if self._host_wait:
+            if self.pool is not None:
                 # hand the batch over only when its preparation has FINISHED on the GPU (this is the worker thread; it sleeps in the runtime
                 # with the interpreter lock released): next() then needs no stream-side wait, and the training stream's queue carries no
                 # cross-queue dependency at all
-                self._arena_mod._host_wait(ev)
+                ev.synchronize()
         return batch, ev, slot
 
     def kick(self):
@@ -222,7 +211,7 @@ class InputPrefetcher:
         self.pending = self.pool.submit(self._prepare) if self.pool is not None else self._prepare()
 
     def next(self):
-        """The next prepared batch.  LIFETIME: with the arena (the default) every device tensor the pipeline built for the PREVIOUS batch -
+        """The next prepared batch.  LIFETIME: every device tensor the pipeline built for the PREVIOUS batch -
         voxels, voxel_coords, voxel_num_points, every neighbour table and the out_indices inside sparse tensors derived from it - lives in
         a slot that this call hands back: the worker overwrites it as soon as the work enqueued so far on the caller's stream has
         finished.  A caller that holds a batch across next() (gradient accumulation over two batches, an evaluation loop that collects

@@ -51,8 +51,6 @@ class BaseBEVBackbone(nn.Module):
 
     def forward(self, data_dict):
         x = data_dict["spatial_features"]
-        if getattr(self, "dense_channels_last", False):
-            x = x.contiguous(memory_format=torch.channels_last)
         h0 = x.shape[2]
         ups, pre = [], []
         # the deblocks end in BatchNorm2d + ReLU (reference :95-102): on the GPU in training mode those tails write their channels of the

@@ -4,8 +4,7 @@
     python -m toda_amd.tools.bench_kernels [--workload c3] [--iters 5]
 
 Prints one line per (operator, shape): mean ms, algorithmic GB/s and TFLOP/s.  Used to pick kernel
-variants (the environment knobs TODA_GG_LDS / TODA_WG_SUB / TODA_WG_XCD / TODA_WG_CHUNKS are read once per process by
-libtoda_hip.so - README.md has the table; TODA_HIP_LIB points at an alternative build for A/B runs in one session)."""
+variants (TODA_HIP_LIB points at an alternative build for A/B runs in one session; README.md has the table of switches)."""
 import argparse
 import collections
 import os
@@ -105,9 +104,7 @@ def main():
         step()
     rows = rec.report()
     total = sum(r[0] for r in rows) / args.iters
-    print(f"# {args.workload}: {total:.3f} ms/step inside libtoda_hip.so "
-          f"(TODA_GG_LDS={os.environ.get('TODA_GG_LDS', '1')} TODA_WG_SUB={os.environ.get('TODA_WG_SUB', '7')} "
-          f"TODA_WG_XCD={os.environ.get('TODA_WG_XCD', '1')} TODA_WG_CHUNKS={os.environ.get('TODA_WG_CHUNKS', '0')})")
+    print(f"# {args.workload}: {total:.3f} ms/step inside libtoda_hip.so (TODA_HIP_LIB={os.environ.get('TODA_HIP_LIB', '')})")
     for tot, key, mean, n in rows:
         extra = ""
         if key[0] in ("toda_spconv_gather_gemm", "toda_spconv_gather_gemm_ordered", "toda_spconv_wgrad"):
