@@ -938,6 +938,45 @@ int toda_nusc_eval_match(const double* pred, const double* pred_score, const int
                          const int32_t* seg_cls_host, int n_seg, const double* thresholds_host, int tp_threshold,
                          int32_t* match, double* err, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The device parts of the Waymo detection metric (LEVEL_1 / LEVEL_2 AP and APH per object type; the reference
+ * hands the metric to TensorFlow and the waymo_open_dataset package).  fp64 and integers throughout, no float atomics: two
+ * runs give the same bits.  A segment is one (frame, object type); boxes [., 7] = x y z dx dy dz heading are stored segment
+ * after segment.  pred_off_host / gt_off_host (HOST, int32 [n_seg + 1]) are the CSR offsets of both sides, iou_off_host
+ * (HOST, int64 [n_seg + 1]) those of the segments' [n_pred_s, n_gt_s] row-major IoU blocks, n_pairs = iou_off_host[n_seg].
+ * They are checked on the host (null, negative, descending, a block that is not n_pred_s x n_gt_s, a segment over
+ * TODA_WAYMO_MAX_PRED predictions or TODA_WAYMO_MAX_GT ground truths: refused before anything is launched) and copied into ws.
+ *
+ * toda_waymo_eval_iou: the 7-DOF IoU of every same-segment pair.  Exact convex clipping of the prediction's rectangle by the
+ * four half-planes of the ground truth's, no corner margins; shoelace area times the overlap of the z-intervals;
+ * inter / (volA + volB - inter), 0 when that denominator is not positive, clamped to [0, 1].
+ *
+ * toda_waymo_eval_match: per segment and score cutoff the maximum-weight one-to-one assignment between the predictions with
+ * (fp32) score >= cutoff and the ground truths, on the weights w = IoU >= t ? (int)(IoU * 1000) : 0 with t = 0.7 for type 1
+ * (Vehicle) and 0.5 for types 2..4 (Pedestrian, Sign, Cyclist); a pair is a match iff it is assigned and w > 0.  Where the
+ * optimum is not unique, which optimal assignment is returned is not specified.  seg_type_host (HOST, int32 [n_seg]) holds
+ * 1..4; cutoffs_host (HOST, fp32 [TODA_WAYMO_CUTOFFS]) must ascend; gt_level [n_gt] is the difficulty, a ground truth is in
+ * level L iff it is <= L.  Summed over the segments of a type in a fixed order:
+ *   tp, fn  int64 [4, 2, 101]   matched / unmatched ground truths in level (type - 1, level - 1, cutoff)
+ *   fp      int64 [4, 101]      unmatched active predictions (one matched to a ground truth above the level counts nowhere)
+ *   sum_ha  fp64  [4, 2, 101]   over the TPs: 1 - min(d, 2 pi - d) / pi, d = |heading difference| mod 2 pi
+ * match_dbg (may be NULL): int32 [101, n_pred], at every cutoff the row in the ground-truth arrays each prediction is matched
+ * to, -1 when unmatched or inactive.
+ * ws: toda_waymo_eval_match_workspace_bytes(n_seg) bytes, for either call.
+ * ---------------------------------------------------------------------- */
+#define TODA_WAYMO_MAX_PRED 512
+#define TODA_WAYMO_MAX_GT 512
+#define TODA_WAYMO_CUTOFFS 101
+size_t toda_waymo_eval_match_workspace_bytes(int n_seg);
+int toda_waymo_eval_iou(const double* pred, int n_pred, const double* gt, int n_gt, const int32_t* pred_off_host,
+                        const int32_t* gt_off_host, const long long* iou_off_host, int n_seg, long long n_pairs, double* iou,
+                        void* ws, size_t ws_bytes, void* stream);
+int toda_waymo_eval_match(const double* iou, const float* pred_score, const double* pred_heading, int n_pred,
+                          const double* gt_heading, const int32_t* gt_level, int n_gt, const int32_t* pred_off_host,
+                          const int32_t* gt_off_host, const long long* iou_off_host, const int32_t* seg_type_host, int n_seg,
+                          long long n_pairs, const float* cutoffs_host, long long* tp, long long* fn, long long* fp,
+                          double* sum_ha, int32_t* match_dbg, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -172,6 +172,9 @@ SIGNATURES = {
     "toda_nusc_eval_prepare": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "toda_nusc_eval_match_workspace_bytes": (_sz, [_i]),
     "toda_nusc_eval_match": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "toda_waymo_eval_match_workspace_bytes": (_sz, [_i]),
+    "toda_waymo_eval_iou": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, C.c_longlong, _vp, _vp, _sz, _vp]),
+    "toda_waymo_eval_match": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, C.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

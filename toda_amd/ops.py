@@ -1965,6 +1965,80 @@ def nusc_eval_match(pred, score, pred_attr, gt, gt_attr, pred_off, gt_off, seg_c
     return match, err
 
 
+WAYMO_MAX_PRED, WAYMO_MAX_GT, WAYMO_CUTOFFS = 512, 512, 101      # TODA_WAYMO_* of include/toda.h
+WAYMO_TYPES = ("Vehicle", "Pedestrian", "Sign", "Cyclist")       # estimator types 1..4
+
+
+def waymo_score_cutoffs():
+    """The metric's 101 score cutoffs as the estimator holds them: fp32(k * 0.01) for k = 0..99, and 1."""
+    return np.concatenate([np.arange(100, dtype=np.float64) * 0.01, [1.0]]).astype(np.float32)
+
+
+def _waymo_offsets(pred_off, gt_off, who):
+    pred_off, gt_off = (np.ascontiguousarray(a, dtype=np.int32) for a in (pred_off, gt_off))
+    if pred_off.ndim != 1 or pred_off.shape != gt_off.shape or pred_off.shape[0] < 1:
+        raise RuntimeError(f"{who}: pred_off and gt_off must be [n_seg + 1]")
+    iou_off = np.zeros(pred_off.shape[0], dtype=np.int64)
+    np.cumsum(np.diff(pred_off).astype(np.int64) * np.diff(gt_off).astype(np.int64), out=iou_off[1:])
+    return pred_off, gt_off, iou_off
+
+
+def waymo_eval_iou(pred, gt, pred_off, gt_off):
+    """The Waymo metric's 7-DOF IoU of every same-segment pair (toda_waymo_eval_iou) -> flat fp64; segment s's [n_pred_s, n_gt_s]
+    block starts at sum over earlier segments of n_pred * n_gt.  pred / gt fp64 [., 7] = x y z dx dy dz heading in segment order;
+    pred_off / gt_off are HOST int32 CSR offsets [n_seg + 1]."""
+    lib = L.load()
+    pred, gt = (_eval_arg(t, torch.float64, "waymo_eval_iou: boxes") for t in (pred, gt))
+    if pred.dim() != 2 or pred.shape[1] != 7 or gt.dim() != 2 or gt.shape[1] != 7:
+        raise RuntimeError("waymo_eval_iou: pred and gt must be [., 7]")
+    pred_off, gt_off, iou_off = _waymo_offsets(pred_off, gt_off, "waymo_eval_iou")
+    n_seg, n_pairs = int(pred_off.shape[0]) - 1, int(iou_off[-1])
+    iou = torch.empty((n_pairs,), dtype=torch.float64, device=pred.device)
+    ws_bytes = lib.toda_waymo_eval_match_workspace_bytes(n_seg)
+    ws = torch.empty((max(int(ws_bytes), 1),), dtype=torch.uint8, device=pred.device)
+    rc = lib.toda_waymo_eval_iou(L.ptr(pred), int(pred.shape[0]), L.ptr(gt), int(gt.shape[0]), pred_off.ctypes.data, gt_off.ctypes.data,
+                                 iou_off.ctypes.data, n_seg, n_pairs, L.ptr(iou), L.ptr(ws), ws_bytes, L.stream())
+    L.check(rc, "toda_waymo_eval_iou")
+    torch.cuda.current_stream().synchronize()           # the host offsets have been read once the copies into ws are done
+    return iou
+
+
+def waymo_eval_match(iou, score, pred_heading, gt_heading, gt_level, pred_off, gt_off, seg_type, cutoffs=None, debug=False):
+    """The Waymo metric's matching at the 101 score cutoffs (toda_waymo_eval_match) -> (tp int64 [4, 2, 101], fn int64 [4, 2, 101],
+    fp int64 [4, 101], sum_ha fp64 [4, 2, 101], match int32 [101, n_pred] or None): type - 1, level - 1, cutoff.  iou as
+    waymo_eval_iou lays it out; score fp32 [n_pred]; headings fp64; gt_level int32 [n_gt] (the difficulty); pred_off / gt_off /
+    seg_type (1 Vehicle, 2 Pedestrian, 3 Sign, 4 Cyclist) are HOST int32 arrays.  debug: also the match table, the row of the
+    ground truth each prediction is assigned to at each cutoff, -1 when unmatched or inactive."""
+    lib = L.load()
+    iou, pred_heading, gt_heading = (_eval_arg(t, torch.float64, "waymo_eval_match: IoU and headings") for t in (iou, pred_heading, gt_heading))
+    score = _eval_arg(score, torch.float32, "waymo_eval_match: score")
+    gt_level = _eval_arg(gt_level, torch.int32, "waymo_eval_match: gt_level")
+    pred_off, gt_off, iou_off = _waymo_offsets(pred_off, gt_off, "waymo_eval_match")
+    seg_type = np.ascontiguousarray(seg_type, dtype=np.int32)
+    cuts = np.ascontiguousarray(waymo_score_cutoffs() if cutoffs is None else cutoffs, dtype=np.float32)
+    n_seg, n_pairs = int(pred_off.shape[0]) - 1, int(iou_off[-1])
+    n_pred, n_gt = int(score.numel()), int(gt_level.numel())
+    if seg_type.shape != (n_seg,) or cuts.shape != (WAYMO_CUTOFFS,):
+        raise RuntimeError(f"waymo_eval_match: one type per segment and {WAYMO_CUTOFFS} cutoffs")
+    if pred_heading.numel() != n_pred or gt_heading.numel() != n_gt or iou.numel() != n_pairs:
+        raise RuntimeError("waymo_eval_match: one heading per box, and the IoU blocks of the offsets")
+    dev = score.device
+    tp = torch.empty((4, 2, WAYMO_CUTOFFS), dtype=torch.int64, device=dev)
+    fn = torch.empty((4, 2, WAYMO_CUTOFFS), dtype=torch.int64, device=dev)
+    fp = torch.empty((4, WAYMO_CUTOFFS), dtype=torch.int64, device=dev)
+    sum_ha = torch.empty((4, 2, WAYMO_CUTOFFS), dtype=torch.float64, device=dev)
+    match = torch.empty((WAYMO_CUTOFFS, n_pred), dtype=torch.int32, device=dev) if debug else None
+    ws_bytes = lib.toda_waymo_eval_match_workspace_bytes(n_seg)
+    ws = torch.empty((max(int(ws_bytes), 1),), dtype=torch.uint8, device=dev)
+    rc = lib.toda_waymo_eval_match(L.ptr(iou), L.ptr(score), L.ptr(pred_heading), n_pred, L.ptr(gt_heading), L.ptr(gt_level), n_gt,
+                                   pred_off.ctypes.data, gt_off.ctypes.data, iou_off.ctypes.data, seg_type.ctypes.data, n_seg, n_pairs,
+                                   cuts.ctypes.data, L.ptr(tp), L.ptr(fn), L.ptr(fp), L.ptr(sum_ha), L.ptr(match), L.ptr(ws), ws_bytes,
+                                   L.stream())
+    L.check(rc, "toda_waymo_eval_match")
+    torch.cuda.current_stream().synchronize()           # the host arrays have been read once the copies into ws are done
+    return tp, fn, fp, sum_ha, match
+
+
 class _CenterLoss(torch.autograd.Function):
     """CenterHead.get_loss of one head group in three launches forward / one backward (toda_center_loss_*).
     apply(n, hm_logits, reg_0..reg_{n-1}, heatmap, inds, mask, target_boxes, code_weights, cls_weight, loc_weight)

@@ -1,6 +1,6 @@
 """WaymoDataset (behaviour of reference pcdet/datasets/waymo/waymo_dataset.py): the processed Waymo Open Dataset frames on disk
 and the per-sequence info pickles of a stock OpenPCDet preparation (v0.5.0) -> training / evaluation samples, the GT-sampling
-database, prediction dicts and the KITTI-style AP.
+database, prediction dicts, the KITTI-style AP and the Waymo LEVEL_1 / LEVEL_2 AP / APH (eval_metric 'aph', waymo_eval.py).
 
     <DATA_PATH>/ImageSets/{train,val}.txt                                   one sequence per line (segment-..._with_camera_labels.tfrecord)
     <DATA_PATH>/<PROCESSED_DATA_TAG>/<sequence>/<sequence>.pkl              list of {point_cloud {lidar_sequence, sample_idx}, frame_id,
@@ -17,8 +17,8 @@ get_lidar_host is the same work in the reference's numpy statements: the test or
 intensity is (float)tanh((double)i), the correctly rounded value; numpy's fp32 tanh lies within an ulp of it.
 
 Not built: the info builder from TFRecords (create_waymo_infos; it needs TensorFlow and the waymo_open_dataset package), the
-Waymo L1 / L2 metric (eval_metric 'waymo' raises ImportError naming those packages; eval_metric 'kitti' is served), and the
-shared-memory frame cache: USE_SHARED_MEMORY of the dataset is accepted and ignored, frames already live in HBM.
+estimator route of the Waymo L1 / L2 metric (eval_metric 'waymo' raises ImportError naming those packages; eval_metric 'aph' is
+the same metric on the project's own kernels, eval_metric 'kitti' the KITTI table), and the shared-memory frame cache: USE_SHARED_MEMORY of the dataset is accepted and ignored, frames already live in HBM.
 
     python -m toda_amd.pcdet.datasets.waymo.waymo_dataset create_waymo_gt_database <dataset yaml> [--data_path DIR] [--processed_data_tag TAG]
 """
@@ -189,9 +189,11 @@ class WaymoDataset(DatasetTemplate):
         if metric == "kitti":
             gt_annos = [common_utils.drop_info_with_name(copy.deepcopy(info["annos"]), name="unknown") for info in self.infos]
             return self.kitti_eval(copy.deepcopy(det_annos), gt_annos, class_names)
+        if metric == "aph":
+            return self.aph_eval(det_annos, class_names, route=kwargs.get("eval_route", "device"))
         if metric == "waymo":
             return self.waymo_eval(det_annos, class_names, **kwargs)
-        raise NotImplementedError(f"eval_metric '{metric}': WaymoDataset scores with 'kitti' (or 'waymo' through the Waymo Open Dataset estimator)")
+        raise NotImplementedError(f"eval_metric '{metric}': WaymoDataset scores with 'kitti', 'aph' (or 'waymo' through the Waymo Open Dataset estimator)")
 
     def kitti_eval(self, eval_det_annos, eval_gt_annos, class_names):
         """The KITTI AP table in the LiDAR frame: detections and infos pair up by position, Vehicle scores as Car, every object
@@ -210,6 +212,13 @@ class WaymoDataset(DatasetTemplate):
                                                           info_with_fakelidar=self.dataset_cfg.get("INFO_WITH_FAKELIDAR", False))
         return kitti_eval.get_official_eval_result(eval_gt_annos, eval_det_annos, [MAP_NAME_TO_KITTI[c] for c in class_names])
 
+    def aph_eval(self, det_annos, class_names, route="device"):
+        """LEVEL_1 / LEVEL_2 AP and APH per object type (waymo_eval.py, DESIGN.md 3.15): detections and infos pair up by position;
+        neither is changed.  route 'host' is the numpy / scipy statement of the same metric."""
+        from . import waymo_eval
+        return waymo_eval.evaluate(det_annos, [info["annos"] for info in self.infos], class_names,
+                                   info_with_fakelidar=self.dataset_cfg.get("INFO_WITH_FAKELIDAR", False), route=route)
+
     def waymo_eval(self, det_annos, class_names, **kwargs):
         try:
             import tensorflow  # noqa: F401
@@ -217,8 +226,8 @@ class WaymoDataset(DatasetTemplate):
         except ImportError as e:
             raise ImportError("eval_metric 'waymo' (L1 / L2 AP and APH) runs the detection metrics estimator of the Waymo Open Dataset "
                               "(packages tensorflow and waymo-open-dataset, modules `tensorflow` and `waymo_open_dataset`), which are "
-                              "not installed; score with eval_metric 'kitti' instead") from e
-        raise NotImplementedError("the Waymo Open Dataset estimator is not wired up: score with eval_metric 'kitti'")
+                              "not installed; score with eval_metric 'aph' (the same metric on this project's kernels) or 'kitti' instead") from e
+        raise NotImplementedError("the Waymo Open Dataset estimator is not wired up: score with eval_metric 'aph' or 'kitti'")
 
     # ---- GT database: the frames of an infos pickle through augmentor/database_sampler.create_groundtruth_database
     def create_groundtruth_database(self, info_path, save_path, used_classes=None, split="train", sampled_interval=10,
