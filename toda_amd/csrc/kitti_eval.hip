@@ -13,15 +13,14 @@
 //
 // eval_match_kernel: one wavefront per (frame, score threshold).  Ground truths are visited in order (an earlier match takes
 // its detection away from a later one); the detections of one ground truth are reduced across the wave by a rule without
-// carried state (see ev_pick).  The wave's counts and its AOS sum go to a [F, T, 4] slab of doubles; eval_fold_kernel adds the
-// frames up in one fixed order, so two runs give the same bits.  No atomics anywhere.
-#include "common.h"
+// carried state (see ev_better; the ladder is eval_common.cuh's wave_best).  The wave's counts and its AOS sum go to a [F, T, 4] slab of
+// doubles; eval_fold_kernel adds the frames up in one fixed order (fold_runs), so two runs give the same bits.  No atomics anywhere.
+#include "eval_common.cuh"
 
 namespace toda {
 
 constexpr int EV_BLOCK = 256;
-constexpr int EV_WAVE = 64;
-constexpr int EV_WAVES = EV_BLOCK / EV_WAVE;
+constexpr int EV_WAVES = EV_BLOCK / EVAL_WAVE;
 constexpr int EV_MAX_PTS = 24;     // 4 + 4 corners, 4 x 4 edge crossings
 
 struct EvPt {
@@ -200,30 +199,13 @@ struct EvPick {
     int cls;      // 2: a detection that counts, 1: an ignored one (height below the difficulty's minimum), 0: none
     double val;   // what is maximised inside cls 2
     int idx;
+    __device__ EvPick across(int m) const { return {__shfl_xor(cls, m, EVAL_WAVE), __shfl_xor(val, m, EVAL_WAVE), __shfl_xor(idx, m, EVAL_WAVE)}; }
 };
 
 __device__ __forceinline__ bool ev_better(const EvPick& a, const EvPick& b) {   // a before b
     if (a.cls != b.cls) return a.cls > b.cls;
     if (a.val != b.val) return a.val > b.val;
     return a.idx < b.idx;
-}
-
-__device__ __forceinline__ EvPick ev_wave_best(EvPick p) {
-#pragma unroll
-    for (int m = EV_WAVE / 2; m >= 1; m >>= 1) {
-        EvPick o;
-        o.cls = __shfl_xor(p.cls, m, EV_WAVE);
-        o.val = __shfl_xor(p.val, m, EV_WAVE);
-        o.idx = __shfl_xor(p.idx, m, EV_WAVE);
-        if (ev_better(o, p)) p = o;
-    }
-    return p;
-}
-
-__device__ __forceinline__ int ev_wave_sum(int v) {
-#pragma unroll
-    for (int m = EV_WAVE / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, EV_WAVE);
-    return v;
 }
 
 struct EvMatch {
@@ -255,8 +237,8 @@ template <bool FP>
 __global__ __launch_bounds__(EV_BLOCK) void eval_match_kernel(EvMatch p, unsigned char* __restrict__ assigned_ws,
                                                                double* __restrict__ partial, double* __restrict__ scores_out,
                                                                int32_t* __restrict__ count_out) {
-    const int lane = threadIdx.x & (EV_WAVE - 1);
-    const long long item = (long long)blockIdx.x * EV_WAVES + (threadIdx.x / EV_WAVE);
+    const int lane = threadIdx.x & (EVAL_WAVE - 1);
+    const long long item = (long long)blockIdx.x * EV_WAVES + (threadIdx.x / EVAL_WAVE);
     if (item >= (long long)p.n_frames * p.n_thresh) return;       // whole waves leave: no barrier below
     const int f = (int)(item / p.n_thresh), t = (int)(item - (long long)f * p.n_thresh);
     const int d0 = p.det_off[f], nd = p.det_off[f + 1] - d0;
@@ -266,14 +248,14 @@ __global__ __launch_bounds__(EV_BLOCK) void eval_match_kernel(EvMatch p, unsigne
     const double* score = p.score + d0;
     unsigned char* assigned = assigned_ws + (size_t)t * p.n_det_total + d0;
     const double thresh = FP ? p.thresh[t] : 0.0;
-    for (int j = lane; j < nd; j += EV_WAVE) assigned[j] = 0;
+    for (int j = lane; j < nd; j += EVAL_WAVE) assigned[j] = 0;
     int tp = 0, fn = 0;
     double sim = 0.0;
     for (int i = 0; i < ng; ++i) {
         const int ig = p.ign_gt[g0 + i];
         if (ig == -1) continue;
         EvPick best = {0, 0.0, 0x7fffffff};
-        for (int j = lane; j < nd; j += EV_WAVE) {
+        for (int j = lane; j < nd; j += EVAL_WAVE) {
             const int id = ign_det[j];
             if (id == -1 || assigned[j]) continue;
             if (FP && score[j] < thresh) continue;
@@ -290,13 +272,13 @@ __global__ __launch_bounds__(EV_BLOCK) void eval_match_kernel(EvMatch p, unsigne
             c.idx = j;
             if (ev_better(c, best)) best = c;
         }
-        best = ev_wave_best(best);
+        best = wave_best(best, ev_better);
         if (best.cls == 0) {
             if (ig == 0) ++fn;
             continue;
         }
         const int di = best.idx;
-        if ((di & (EV_WAVE - 1)) == lane) assigned[di] = 1;
+        if ((di & (EVAL_WAVE - 1)) == lane) assigned[di] = 1;
         if (ig == 1 || ign_det[di] == 1) continue;
         if (!FP) {
             if (lane == 0) scores_out[g0 + tp] = score[di];
@@ -312,7 +294,7 @@ __global__ __launch_bounds__(EV_BLOCK) void eval_match_kernel(EvMatch p, unsigne
     // false positives: counting detections left over, minus those a DontCare region covers (image metric only)
     const int c0 = p.use_dc ? p.dc_off[f] : 0, nc = p.use_dc ? p.dc_off[f + 1] - c0 : 0;
     int fp = 0;
-    for (int j = lane; j < nd; j += EV_WAVE) {
+    for (int j = lane; j < nd; j += EVAL_WAVE) {
         if (assigned[j] || ign_det[j] != 0 || score[j] < thresh) continue;
         bool stuff = false;
         const double* b = p.det_bbox + (size_t)(d0 + j) * 4;
@@ -324,7 +306,7 @@ __global__ __launch_bounds__(EV_BLOCK) void eval_match_kernel(EvMatch p, unsigne
         }
         if (!stuff) ++fp;
     }
-    fp = ev_wave_sum(fp);
+    fp = wave_sum(fp);
     if (lane == 0) {
         double* dst = partial + ((size_t)f * p.n_thresh + t) * 4;
         dst[0] = tp;
@@ -339,18 +321,18 @@ __global__ __launch_bounds__(EV_BLOCK) void eval_fold_kernel(const double* __res
                                                               double* __restrict__ pr) {
     __shared__ double s[EV_BLOCK];
     const int t = blockIdx.x, c = blockIdx.y;
-    const int run = (n_frames + EV_BLOCK - 1) / EV_BLOCK;
-    const int lo = threadIdx.x * run, hi = min(lo + run, n_frames);
-    double acc = 0.0;
-    for (int f = lo; f < hi; ++f) acc += partial[((size_t)f * n_thresh + t) * 4 + c];
-    s[threadIdx.x] = acc;
-    __syncthreads();
-    for (int m = EV_BLOCK / 2; m >= 1; m >>= 1) {
-        if ((int)threadIdx.x < m) s[threadIdx.x] += s[threadIdx.x + m];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) pr[t * 4 + c] = s[0];
+    const double sum = fold_runs<double, EV_BLOCK>(n_frames, [&](int f) { return partial[((size_t)f * n_thresh + t) * 4 + c]; }, s);
+    if (threadIdx.x == 0) pr[t * 4 + c] = sum;
 }
+
+// ws: partial [F, T, 4] doubles | assigned [T, n_det_total] bytes | one spare slot (part of the size this export has always returned)
+struct EvWs {
+    WsCarver c;
+    size_t partial, assigned, spare;
+    EvWs(int n_frames, int n_thresh, int n_det_total)
+        : partial(c.take((size_t)n_frames * n_thresh * 4 * sizeof(double))), assigned(c.take((size_t)n_thresh * n_det_total)),
+          spare(c.take(256)) {}
+};
 
 }  // namespace toda
 
@@ -374,7 +356,7 @@ extern "C" int toda_eval_overlaps(const float* box3d, const float* bbox, const i
 
 extern "C" size_t toda_eval_match_workspace_bytes(int n_frames, int n_thresh, int n_det_total) {
     if (n_frames < 1 || n_thresh < 1 || n_det_total < 0) return 0;
-    return align_up((size_t)n_frames * n_thresh * 4 * sizeof(double), 256) + align_up((size_t)n_thresh * n_det_total, 256) + 256;
+    return EvWs(n_frames, n_thresh, n_det_total).c.at;
 }
 
 static int ev_fill(EvMatch& p, const char* who, const float* overlaps, const long long* ov_off, const int32_t* det_off,
@@ -409,7 +391,7 @@ extern "C" int toda_eval_match_scores(const float* overlaps, const long long* ov
     TODA_CHECK_ARG(ws && ws_bytes >= toda_eval_match_workspace_bytes(n_frames, 1, n_det_total),
                    "eval_match_scores: workspace too small");
     p.n_thresh = 1;
-    unsigned char* assigned = (unsigned char*)ws + align_up((size_t)n_frames * 4 * sizeof(double), 256);
+    unsigned char* assigned = (unsigned char*)ws + EvWs(n_frames, 1, n_det_total).assigned;
     hipLaunchKernelGGL(eval_match_kernel<false>, dim3(cdiv(n_frames, EV_WAVES)), dim3(EV_BLOCK), 0, (hipStream_t)stream, p,
                        assigned, (double*)nullptr, scores_out, count_out);
     TODA_LAUNCH_CHECK();
@@ -449,8 +431,9 @@ extern "C" int toda_eval_match(const float* overlaps, const long long* ov_off, c
     p.n_thresh = n_thresh;
     p.use_dc = metric == 0 ? 1 : 0;
     p.aos = compute_aos ? 1 : 0;
-    double* partial = (double*)ws;
-    unsigned char* assigned = (unsigned char*)ws + align_up((size_t)n_frames * n_thresh * 4 * sizeof(double), 256);
+    const EvWs w(n_frames, n_thresh, n_det_total);
+    double* partial = (double*)((char*)ws + w.partial);
+    unsigned char* assigned = (unsigned char*)ws + w.assigned;
     hipLaunchKernelGGL(eval_match_kernel<true>, dim3(cdiv((long long)n_frames * n_thresh, EV_WAVES)), dim3(EV_BLOCK), 0, s, p,
                        assigned, partial, (double*)nullptr, (int32_t*)nullptr);
     TODA_LAUNCH_CHECK();

@@ -11,18 +11,17 @@
 // pass over all scores per prediction) is cheaper than a sort.  Each wave then walks the predictions in that order.  Lane l owns
 // ground truths l, l + 64, ... and keeps their taken bits in one 32-bit register, hence NUSC_MAX_GT = 64 * 32 = 2048 ground
 // truths per segment.  The nearest free ground truth is the lexicographic minimum of (distance, index) over the wave: six
-// shuffle steps.  It is a match iff the distance is strictly below the threshold; otherwise the prediction is a false positive
-// and takes nothing.  The wave of the true-positive threshold also writes the five errors of each match.
-#include "common.h"
+// shuffle steps.  It is a match iff the distance is strictly below the threshold; otherwise the prediction takes nothing.  The wave
+// of the true-positive threshold also writes each match's five errors.  Rank, minimum and segment guard are eval_common.cuh's.
+#include "eval_common.cuh"
 
 namespace toda {
 
 constexpr int NE_BLOCK = 256;
-constexpr int NE_WAVE = 64;
-constexpr int NE_THRESH = NE_BLOCK / NE_WAVE;          // 4 thresholds: one wave each
+constexpr int NE_THRESH = NE_BLOCK / EVAL_WAVE;          // 4 thresholds: one wave each
 constexpr int NE_MAX_PRED = TODA_NUSC_MAX_PRED;        // 500
 constexpr int NE_MAX_GT = TODA_NUSC_MAX_GT;            // 2048
-constexpr int NE_SLOTS = NE_MAX_GT / NE_WAVE;          // 32: the bits of a lane's taken mask
+constexpr int NE_SLOTS = NE_MAX_GT / EVAL_WAVE;          // 32: the bits of a lane's taken mask
 constexpr int NE_CLASSES = 10;
 constexpr int NE_BARRIER = 9;
 constexpr int NE_ROW = 10;                             // prepare input: x y z dx dy dz heading vx vy vz
@@ -69,18 +68,10 @@ __global__ __launch_bounds__(NE_BLOCK) void nusc_eval_prepare_kernel(const doubl
 struct NePick {
     double d;
     int idx;
+    __device__ NePick across(int m) const { return {__shfl_xor(d, m, EVAL_WAVE), __shfl_xor(idx, m, EVAL_WAVE)}; }
 };
 
-__device__ __forceinline__ NePick ne_wave_min(NePick p) {
-#pragma unroll
-    for (int m = NE_WAVE / 2; m >= 1; m >>= 1) {
-        NePick o;
-        o.d = __shfl_xor(p.d, m, NE_WAVE);
-        o.idx = __shfl_xor(p.idx, m, NE_WAVE);
-        if (o.d < p.d || (o.d == p.d && o.idx < p.idx)) p = o;
-    }
-    return p;
-}
+__device__ __forceinline__ bool ne_nearer(const NePick& a, const NePick& b) { return a.d < b.d || (a.d == b.d && a.idx < b.idx); }
 
 // floored remainder x mod p for p > 0
 __device__ __forceinline__ double ne_mod(double x, double p) {
@@ -98,7 +89,7 @@ struct NeMatch {
     const int32_t* pred_off;     // [n_seg + 1]
     const int32_t* gt_off;       // [n_seg + 1]
     const int32_t* seg_cls;      // [n_seg]
-    int n_seg, n_pred, n_gt, tp_wave;
+    int n_pred, n_gt, tp_wave;
     double thresh[NE_THRESH];
 };
 
@@ -107,10 +98,9 @@ __global__ __launch_bounds__(NE_BLOCK) void nusc_eval_match_kernel(NeMatch p, in
     __shared__ double s_xy[NE_MAX_PRED][2];
     __shared__ int s_order[NE_MAX_PRED];
     const int seg = blockIdx.x;
-    const int p0 = p.pred_off[seg], np = p.pred_off[seg + 1] - p0;
-    const int g0 = p.gt_off[seg], ng = p.gt_off[seg + 1] - g0;
     // the launcher has checked the offsets on the host; a segment outside the buffers or the LDS arrays is left alone
-    if (np <= 0 || np > NE_MAX_PRED || ng < 0 || ng > NE_MAX_GT || p0 < 0 || g0 < 0 || p0 + np > p.n_pred || g0 + ng > p.n_gt) return;
+    const auto [p0, np, g0, ng, inside] = seg_span(p.pred_off, p.gt_off, seg, p.n_pred, p.n_gt, NE_MAX_PRED, NE_MAX_GT);
+    if (!inside || np <= 0) return;
     for (int i = threadIdx.x; i < np; i += NE_BLOCK) {
         s_score[i] = p.score[p0 + i];
         s_xy[i][0] = p.pred[(size_t)(p0 + i) * NE_BOX];
@@ -118,23 +108,15 @@ __global__ __launch_bounds__(NE_BLOCK) void nusc_eval_match_kernel(NeMatch p, in
         s_order[i] = -1;
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < np; i += NE_BLOCK) {
-        const double si = s_score[i];
-        int rank = 0;
-        for (int j = 0; j < np; ++j) {
-            const double sj = s_score[j];
-            rank += (sj > si || (sj == si && j > i)) ? 1 : 0;
-        }
-        s_order[rank] = i;                              // a total order (finite scores): every rank is written once
-    }
-    __syncthreads();
+    rank_by_score<true>(s_score, s_order, np, threadIdx.x, NE_BLOCK);     // equal scores: the later position first; the host refuses
+    __syncthreads();                                                      // non-finite scores, so the order is total
 
-    const int lane = threadIdx.x & (NE_WAVE - 1), wave = threadIdx.x / NE_WAVE;
+    const int lane = threadIdx.x & (EVAL_WAVE - 1), wave = threadIdx.x / EVAL_WAVE;
     const double thresh = p.thresh[wave];
     const bool write_err = wave == p.tp_wave;
     const double period = p.seg_cls[seg] == NE_BARRIER ? NE_PI : 2 * NE_PI;
     const double* gt = p.gt + (size_t)g0 * NE_BOX;
-    const int slots = (ng + NE_WAVE - 1) / NE_WAVE;
+    const int slots = (ng + EVAL_WAVE - 1) / EVAL_WAVE;
     // the first slot (every ground truth of a segment with at most 64 of them) stays in registers
     const double gx0 = lane < ng ? gt[(size_t)lane * NE_BOX] : 0.0, gy0 = lane < ng ? gt[(size_t)lane * NE_BOX + 1] : 0.0;
     int32_t* out = match + (size_t)wave * p.n_pred + p0;
@@ -145,7 +127,7 @@ __global__ __launch_bounds__(NE_BLOCK) void nusc_eval_match_kernel(NeMatch p, in
         const double px = s_xy[i][0], py = s_xy[i][1];
         NePick best = {HUGE_VAL, 0x7fffffff};
         for (int k = 0; k < slots; ++k) {
-            const int g = k * NE_WAVE + lane;
+            const int g = k * EVAL_WAVE + lane;
             if (g >= ng || (taken >> k & 1u)) continue;
             const double dx = (k == 0 ? gx0 : gt[(size_t)g * NE_BOX]) - px, dy = (k == 0 ? gy0 : gt[(size_t)g * NE_BOX + 1]) - py;
             const double d = sqrt(dx * dx + dy * dy);
@@ -154,9 +136,9 @@ __global__ __launch_bounds__(NE_BLOCK) void nusc_eval_match_kernel(NeMatch p, in
                 best.idx = g;
             }
         }
-        best = ne_wave_min(best);
+        best = wave_best(best, ne_nearer);
         const bool hit = best.d < thresh;
-        if (hit && (best.idx & (NE_WAVE - 1)) == lane) taken |= 1u << (best.idx / NE_WAVE);
+        if (hit && (best.idx & (EVAL_WAVE - 1)) == lane) taken |= 1u << (best.idx / EVAL_WAVE);
         if (lane == 0) out[i] = hit ? g0 + best.idx : -1;
         if (lane != 0 || !write_err) continue;          // the shuffles above are behind this prediction: lanes rejoin at the loop head
         double e[5];
@@ -180,6 +162,15 @@ __global__ __launch_bounds__(NE_BLOCK) void nusc_eval_match_kernel(NeMatch p, in
     }
 }
 
+// ws: pred_off | gt_off | seg_cls
+struct NeWs {
+    WsCarver c;
+    size_t pred_off, gt_off, seg_cls;
+    explicit NeWs(int n_seg)
+        : pred_off(c.take((size_t)(n_seg + 1) * sizeof(int32_t))), gt_off(c.take((size_t)(n_seg + 1) * sizeof(int32_t))),
+          seg_cls(c.take((size_t)n_seg * sizeof(int32_t))) {}
+};
+
 }  // namespace toda
 
 using namespace toda;
@@ -198,7 +189,7 @@ extern "C" int toda_nusc_eval_prepare(const double* rows, const int32_t* sample,
 
 extern "C" size_t toda_nusc_eval_match_workspace_bytes(int n_seg) {
     if (n_seg < 1) return 0;
-    return 2 * align_up((size_t)(n_seg + 1) * sizeof(int32_t), 256) + align_up((size_t)n_seg * sizeof(int32_t), 256);
+    return NeWs(n_seg).c.at;
 }
 
 extern "C" int toda_nusc_eval_match(const double* pred, const double* pred_score, const int32_t* pred_attr, int n_pred,
@@ -216,34 +207,23 @@ extern "C" int toda_nusc_eval_match(const double* pred, const double* pred_score
     TODA_CHECK_ARG(pred_off_host && gt_off_host && seg_cls_host && thresholds_host, "nusc_eval_match: null offsets, classes or thresholds");
     TODA_CHECK_ARG(tp_threshold >= 0 && tp_threshold < NE_THRESH, "nusc_eval_match: tp_threshold must index the %d thresholds, got %d",
                    NE_THRESH, tp_threshold);
-    TODA_CHECK_ARG(pred_off_host[0] == 0 && gt_off_host[0] == 0 && pred_off_host[n_seg] == n_pred && gt_off_host[n_seg] == n_gt,
-                   "nusc_eval_match: offsets must run from 0 to n_pred / n_gt");
-    for (int s = 0; s < n_seg; ++s) {
-        const int np = pred_off_host[s + 1] - pred_off_host[s], ng = gt_off_host[s + 1] - gt_off_host[s];
-        TODA_CHECK_ARG(np >= 0 && ng >= 0, "nusc_eval_match: offsets of segment %d descend", s);
-        TODA_CHECK_ARG(np <= NE_MAX_PRED, "nusc_eval_match: segment %d has %d predictions, at most %d are ranked", s, np, NE_MAX_PRED);
-        TODA_CHECK_ARG(ng <= NE_MAX_GT, "nusc_eval_match: segment %d has %d ground truths, the taken mask holds %d", s, ng, NE_MAX_GT);
+    // the taken mask holds NE_MAX_GT ground truths, NE_MAX_PRED predictions are ranked
+    if (csr_check("nusc_eval_match", pred_off_host, n_seg, n_pred, NE_MAX_PRED, "predictions") != TODA_OK) return TODA_EINVAL;
+    if (csr_check("nusc_eval_match", gt_off_host, n_seg, n_gt, NE_MAX_GT, "ground truths") != TODA_OK) return TODA_EINVAL;
+    for (int s = 0; s < n_seg; ++s)
         TODA_CHECK_ARG(seg_cls_host[s] >= 0 && seg_cls_host[s] < NE_CLASSES, "nusc_eval_match: class %d of segment %d", seg_cls_host[s], s);
-    }
-    TODA_CHECK_ARG(ws && ws_bytes >= toda_nusc_eval_match_workspace_bytes(n_seg), "nusc_eval_match: workspace too small");
+    const NeWs w(n_seg);
+    TODA_CHECK_ARG(ws && ws_bytes >= w.c.at, "nusc_eval_match: workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    const size_t off_bytes = (size_t)(n_seg + 1) * sizeof(int32_t), off_slot = align_up(off_bytes, 256);
-    int32_t* pred_off = (int32_t*)ws;
-    int32_t* gt_off = (int32_t*)((char*)ws + off_slot);
-    int32_t* seg_cls = (int32_t*)((char*)ws + 2 * off_slot);
-    TODA_HIP(hipMemcpyAsync(pred_off, pred_off_host, off_bytes, hipMemcpyHostToDevice, s));
-    TODA_HIP(hipMemcpyAsync(gt_off, gt_off_host, off_bytes, hipMemcpyHostToDevice, s));
-    TODA_HIP(hipMemcpyAsync(seg_cls, seg_cls_host, (size_t)n_seg * sizeof(int32_t), hipMemcpyHostToDevice, s));
     NeMatch p = {};
+    TODA_HIP(stage(ws, w.pred_off, pred_off_host, n_seg + 1, s, &p.pred_off));
+    TODA_HIP(stage(ws, w.gt_off, gt_off_host, n_seg + 1, s, &p.gt_off));
+    TODA_HIP(stage(ws, w.seg_cls, seg_cls_host, n_seg, s, &p.seg_cls));
     p.pred = pred;
     p.score = pred_score;
     p.pred_attr = pred_attr;
     p.gt = gt;
     p.gt_attr = gt_attr;
-    p.pred_off = pred_off;
-    p.gt_off = gt_off;
-    p.seg_cls = seg_cls;
-    p.n_seg = n_seg;
     p.n_pred = n_pred;
     p.n_gt = n_gt;
     p.tp_wave = tp_threshold;

@@ -9,7 +9,7 @@
 // LDS queue until full waves of them can be clipped.  The order in the queue varies from run to run, a pair's value does not.
 //
 // waymo_eval_match_kernel: one single-wavefront workgroup per segment, so every column scan ends in a shuffle ladder and no step
-// waits for another wave.  The wave ranks the predictions by (score descending, position) in LDS and inserts them one at a time
+// waits for another wave.  The wave ranks the predictions by (score descending, position: rank_by_score<false>) in LDS and inserts them one at a time
 // into a shortest-augmenting-path assignment on the integer costs 1000 - w, w = IoU >= t ? (int)(IoU * 1000) : 0.  Pairs with
 // w = 0 are no edges.  Every prediction has a private "stay free" column of cost 1000; these are not stored: such a column is
 // reachable from its own row only, its dual stays 0, and a row that sits on it can never be entered again, so the nearest of them
@@ -18,12 +18,11 @@
 // ground truths only grows (an augmenting path ends in a free column and frees none), so TP / FN / FP are running counters; the
 // heading sum is taken afresh over the columns at a snapshot whose assignment changed.  Lane l owns columns l, l + 64, ...
 //
-// waymo_eval_fold_kernel: the per-segment snapshot slabs, added per type in one fixed order.
-#include "common.h"
+// waymo_eval_fold_kernel: the per-segment snapshot slabs, added per type in one fixed order (fold_runs).
+#include "eval_common.cuh"
 
 namespace toda {
 
-constexpr int WE_WAVE = 64;
 constexpr int WE_IOU_BLOCK = 256;
 constexpr int WE_IOU_QUEUE = 2048;                     // pairs waiting to be clipped; a tile adds at most WE_IOU_BLOCK
 constexpr int WE_FOLD_BLOCK = 256;
@@ -112,10 +111,9 @@ __global__ __launch_bounds__(WE_IOU_BLOCK) void waymo_eval_iou_kernel(const doub
     __shared__ int s_queue[WE_IOU_QUEUE];
     __shared__ int s_count;
     const int seg = blockIdx.x;
-    const int p0 = pred_off[seg], np = pred_off[seg + 1] - p0;
-    const int g0 = gt_off[seg], ng = gt_off[seg + 1] - g0;
-    // the launcher has checked the offsets on the host; a segment outside the buffers is left alone
-    if (np <= 0 || ng <= 0 || np > WE_MAX_PRED || ng > WE_MAX_GT || p0 < 0 || g0 < 0 || p0 + np > n_pred || g0 + ng > n_gt) return;
+    // the launcher has checked the offsets on the host; a segment outside the buffers is left alone, an empty one has no pairs
+    const auto [p0, np, g0, ng, inside] = seg_span(pred_off, gt_off, seg, n_pred, n_gt, WE_MAX_PRED, WE_MAX_GT);
+    if (!inside || np <= 0 || ng <= 0) return;
     const double* pa = pred + (size_t)p0 * 7;
     const double* gb = gt + (size_t)g0 * 7;
     double* dst = iou + iou_off[seg];
@@ -162,33 +160,19 @@ struct WeMatch {
     const long long* iou_off;    // [n_seg + 1]
     const int32_t* seg_type;     // [n_seg], 1..4
     const float* cutoffs;        // [WE_CUT], ascending
-    int n_seg, n_pred, n_gt;
+    int n_pred, n_gt;
 };
 
 struct WePick {
     int d, idx;
+    __device__ WePick across(int m) const { return {__shfl_xor(d, m, EVAL_WAVE), __shfl_xor(idx, m, EVAL_WAVE)}; }
 };
 
-__device__ __forceinline__ WePick we_wave_min(WePick p) {
-#pragma unroll
-    for (int m = WE_WAVE / 2; m >= 1; m >>= 1) {
-        WePick o;
-        o.d = __shfl_xor(p.d, m, WE_WAVE);
-        o.idx = __shfl_xor(p.idx, m, WE_WAVE);
-        if (o.d < p.d || (o.d == p.d && o.idx < p.idx)) p = o;
-    }
-    return p;
-}
-
-__device__ __forceinline__ double we_wave_sum(double v) {
-#pragma unroll
-    for (int m = WE_WAVE / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, WE_WAVE);
-    return v;
-}
+__device__ __forceinline__ bool we_nearer(const WePick& a, const WePick& b) { return a.d < b.d || (a.d == b.d && a.idx < b.idx); }
 
 __device__ __forceinline__ int we_weight(double iou, double thresh) { return iou >= thresh ? (int)(fmin(iou, 1.0) * 1000.0) : 0; }
 
-__global__ __launch_bounds__(WE_WAVE) void waymo_eval_match_kernel(WeMatch p, int32_t* __restrict__ slab_int, double* __restrict__ slab_ha,
+__global__ __launch_bounds__(EVAL_WAVE) void waymo_eval_match_kernel(WeMatch p, int32_t* __restrict__ slab_int, double* __restrict__ slab_ha,
                                                                    int32_t* __restrict__ match_dbg) {
     __shared__ float s_score[WE_MAX_PRED];
     __shared__ int s_order[WE_MAX_PRED];     // rank -> position in the segment
@@ -204,26 +188,25 @@ __global__ __launch_bounds__(WE_WAVE) void waymo_eval_match_kernel(WeMatch p, in
     __shared__ int s_cnt[WE_INT_ROWS][WE_CUT];
     __shared__ double s_ha[WE_HA_ROWS][WE_CUT];
     const int seg = blockIdx.x, lane = threadIdx.x;
-    const int p0 = p.pred_off[seg], np = p.pred_off[seg + 1] - p0;
-    const int g0 = p.gt_off[seg], ng = p.gt_off[seg + 1] - g0;
     int32_t* out_int = slab_int + (size_t)seg * (WE_INT_ROWS * WE_CUT);
     double* out_ha = slab_ha + (size_t)seg * (WE_HA_ROWS * WE_CUT);
     // the launcher has checked the offsets on the host; a segment outside the buffers or the LDS arrays counts nothing
-    if (np < 0 || np > WE_MAX_PRED || ng < 0 || ng > WE_MAX_GT || p0 < 0 || g0 < 0 || p0 + np > p.n_pred || g0 + ng > p.n_gt) {
-        for (int e = lane; e < WE_INT_ROWS * WE_CUT; e += WE_WAVE) out_int[e] = 0;
-        for (int e = lane; e < WE_HA_ROWS * WE_CUT; e += WE_WAVE) out_ha[e] = 0.0;
+    const auto [p0, np, g0, ng, inside] = seg_span(p.pred_off, p.gt_off, seg, p.n_pred, p.n_gt, WE_MAX_PRED, WE_MAX_GT);
+    if (!inside) {
+        for (int e = lane; e < WE_INT_ROWS * WE_CUT; e += EVAL_WAVE) out_int[e] = 0;
+        for (int e = lane; e < WE_HA_ROWS * WE_CUT; e += EVAL_WAVE) out_ha[e] = 0.0;
         return;
     }
     const double* iou = p.iou + p.iou_off[seg];
     const double thresh = p.seg_type[seg] == 1 ? 0.7 : 0.5;
     int n_l1 = 0, n_l2 = 0;
-    for (int i = lane; i < np; i += WE_WAVE) {
+    for (int i = lane; i < np; i += EVAL_WAVE) {
         const float s = p.score[p0 + i];
         s_score[i] = s == s ? s : -HUGE_VALF;           // a NaN score is below every cutoff, and the order stays total
         s_rowcol[i] = -1;
         s_u[i] = 0;
     }
-    for (int j = lane; j < ng; j += WE_WAVE) {
+    for (int j = lane; j < ng; j += EVAL_WAVE) {
         const int lv = p.gt_level[g0 + j];
         s_level[j] = lv;
         s_v[j] = 0;
@@ -231,22 +214,11 @@ __global__ __launch_bounds__(WE_WAVE) void waymo_eval_match_kernel(WeMatch p, in
         n_l1 += lv <= 1 ? 1 : 0;
         n_l2 += lv <= 2 ? 1 : 0;
     }
-    for (int k = lane; k < WE_CUT; k += WE_WAVE) s_cut[k] = p.cutoffs[k];
-#pragma unroll
-    for (int m = WE_WAVE / 2; m >= 1; m >>= 1) {
-        n_l1 += __shfl_xor(n_l1, m, WE_WAVE);
-        n_l2 += __shfl_xor(n_l2, m, WE_WAVE);
-    }
+    for (int k = lane; k < WE_CUT; k += EVAL_WAVE) s_cut[k] = p.cutoffs[k];
+    n_l1 = wave_sum(n_l1);
+    n_l2 = wave_sum(n_l2);
     __syncthreads();
-    for (int i = lane; i < np; i += WE_WAVE) {
-        const float si = s_score[i];
-        int rank = 0;
-        for (int j = 0; j < np; ++j) {
-            const float sj = s_score[j];
-            rank += (sj > si || (sj == si && j < i)) ? 1 : 0;
-        }
-        s_order[rank] = i;                              // a total order: every rank is written once
-    }
+    rank_by_score<false>(s_score, s_order, np, lane, EVAL_WAVE);            // equal scores: the earlier position first
     __syncthreads();
 
     int tp1 = 0, tp2 = 0, n_match = 0, n_in = 0, k = WE_CUT - 1;
@@ -258,7 +230,7 @@ __global__ __launch_bounds__(WE_WAVE) void waymo_eval_match_kernel(WeMatch p, in
         for (; k >= 0 && (r == np || sc < s_cut[k]); --k) {
             if (ha_stale) {
                 double a1 = 0.0, a2 = 0.0;
-                for (int j = lane; j < ng; j += WE_WAVE) {
+                for (int j = lane; j < ng; j += EVAL_WAVE) {
                     const int row = s_colrow[j];
                     if (row < 0) continue;
                     const double d = fmod(fabs(p.pred_heading[p0 + s_order[row]] - p.gt_heading[g0 + j]), 2 * WE_PI);
@@ -266,8 +238,8 @@ __global__ __launch_bounds__(WE_WAVE) void waymo_eval_match_kernel(WeMatch p, in
                     a1 += s_level[j] <= 1 ? acc : 0.0;
                     a2 += s_level[j] <= 2 ? acc : 0.0;
                 }
-                ha1 = we_wave_sum(a1);
-                ha2 = we_wave_sum(a2);
+                ha1 = wave_sum(a1);
+                ha2 = wave_sum(a2);
                 ha_stale = false;
             }
             if (lane == 0) {
@@ -281,13 +253,13 @@ __global__ __launch_bounds__(WE_WAVE) void waymo_eval_match_kernel(WeMatch p, in
             }
             if (match_dbg) {
                 int32_t* dbg = match_dbg + (size_t)k * p.n_pred + p0;
-                for (int rr = lane; rr < np; rr += WE_WAVE) dbg[s_order[rr]] = (rr < n_in && s_rowcol[rr] >= 0) ? g0 + s_rowcol[rr] : -1;
+                for (int rr = lane; rr < np; rr += EVAL_WAVE) dbg[s_order[rr]] = (rr < n_in && s_rowcol[rr] >= 0) ? g0 + s_rowcol[rr] : -1;
             }
         }
         if (k < 0 || r == np) break;
 
         // insert row r: Dijkstra over the columns on reduced costs, the duals kept current step by step
-        for (int j = lane; j < ng; j += WE_WAVE) {
+        for (int j = lane; j < ng; j += EVAL_WAVE) {
             s_minv[j] = WE_INF;
             s_used[j] = 0;
         }
@@ -303,7 +275,7 @@ __global__ __launch_bounds__(WE_WAVE) void waymo_eval_match_kernel(WeMatch p, in
                 dway = j0;
             }
             WePick best = {WE_INF, 0x7fffffff};
-            for (int j = lane; j < ng; j += WE_WAVE) {
+            for (int j = lane; j < ng; j += EVAL_WAVE) {
                 if (s_used[j]) continue;
                 const int w = we_weight(wrow[j], thresh);
                 int mv = s_minv[j];
@@ -320,10 +292,10 @@ __global__ __launch_bounds__(WE_WAVE) void waymo_eval_match_kernel(WeMatch p, in
                     best.idx = j;
                 }
             }
-            best = we_wave_min(best);
+            best = wave_best(best, we_nearer);
             const bool stay = dmin <= best.d;           // on equal distances the private column: the shorter path
             const int delta = stay ? dmin : best.d;
-            for (int j = lane; j < ng; j += WE_WAVE) {
+            for (int j = lane; j < ng; j += EVAL_WAVE) {
                 if (s_used[j]) {
                     s_u[s_colrow[j]] += delta;
                     s_v[j] -= delta;
@@ -368,8 +340,8 @@ __global__ __launch_bounds__(WE_WAVE) void waymo_eval_match_kernel(WeMatch p, in
         ha_stale = ha_stale || jend >= 0 || dway >= 0;
     }
     __syncthreads();
-    for (int e = lane; e < WE_INT_ROWS * WE_CUT; e += WE_WAVE) out_int[e] = (&s_cnt[0][0])[e];
-    for (int e = lane; e < WE_HA_ROWS * WE_CUT; e += WE_WAVE) out_ha[e] = (&s_ha[0][0])[e];
+    for (int e = lane; e < WE_INT_ROWS * WE_CUT; e += EVAL_WAVE) out_int[e] = (&s_cnt[0][0])[e];
+    for (int e = lane; e < WE_HA_ROWS * WE_CUT; e += EVAL_WAVE) out_ha[e] = (&s_ha[0][0])[e];
 }
 
 // Entry e = row * 101 + cutoff of the slabs (rows tp L1, tp L2, fn L1, fn L2, fp | sum_ha L1, L2), summed over the segments of type
@@ -381,62 +353,34 @@ __global__ __launch_bounds__(WE_FOLD_BLOCK) void waymo_eval_fold_kernel(const in
     __shared__ long long s_i[WE_FOLD_BLOCK];
     __shared__ double s_d[WE_FOLD_BLOCK];
     const int e = blockIdx.x, t = blockIdx.y;
-    const bool is_int = e < WE_INT_ROWS * WE_CUT;
     const int eh = e - WE_INT_ROWS * WE_CUT;
-    const int run = (n_seg + WE_FOLD_BLOCK - 1) / WE_FOLD_BLOCK;
-    const int lo = threadIdx.x * run, hi = min(lo + run, n_seg);
-    long long ai = 0;
-    double ad = 0.0;
-    for (int s = lo; s < hi; ++s) {
-        if (seg_type[s] != t + 1) continue;
-        if (is_int) ai += slab_int[(size_t)s * (WE_INT_ROWS * WE_CUT) + e];
-        else ad += slab_ha[(size_t)s * (WE_HA_ROWS * WE_CUT) + eh];
-    }
-    s_i[threadIdx.x] = ai;
-    s_d[threadIdx.x] = ad;
-    __syncthreads();
-    for (int m = WE_FOLD_BLOCK / 2; m >= 1; m >>= 1) {
-        if ((int)threadIdx.x < m) {
-            s_i[threadIdx.x] += s_i[threadIdx.x + m];
-            s_d[threadIdx.x] += s_d[threadIdx.x + m];
-        }
-        __syncthreads();
-    }
+    // a segment of another type adds 0, which changes no sum: the integers trivially, and an fp64 run that starts at +0 never holds -0
+    const auto load_int = [&](int s) { return seg_type[s] == t + 1 ? (long long)slab_int[(size_t)s * (WE_INT_ROWS * WE_CUT) + e] : 0ll; };
+    const auto load_ha = [&](int s) { return seg_type[s] == t + 1 ? slab_ha[(size_t)s * (WE_HA_ROWS * WE_CUT) + eh] : 0.0; };
+    const long long sum_i = eh < 0 ? fold_runs<long long, WE_FOLD_BLOCK>(n_seg, load_int, s_i) : 0;     // a workgroup folds one side only
+    const double sum_d = eh < 0 ? 0.0 : fold_runs<double, WE_FOLD_BLOCK>(n_seg, load_ha, s_d);
     if (threadIdx.x != 0) return;
     const int row = e / WE_CUT, k = e - row * WE_CUT;
-    if (row < 2) tp[((size_t)t * 2 + row) * WE_CUT + k] = s_i[0];
-    else if (row < 4) fn[((size_t)t * 2 + row - 2) * WE_CUT + k] = s_i[0];
-    else if (row < 5) fp[(size_t)t * WE_CUT + k] = s_i[0];
-    else sum_ha[((size_t)t * 2 + row - 5) * WE_CUT + k] = s_d[0];
+    if (row < 2) tp[((size_t)t * 2 + row) * WE_CUT + k] = sum_i;
+    else if (row < 4) fn[((size_t)t * 2 + row - 2) * WE_CUT + k] = sum_i;
+    else if (row < 5) fp[(size_t)t * WE_CUT + k] = sum_i;
+    else sum_ha[((size_t)t * 2 + row - 5) * WE_CUT + k] = sum_d;
 }
 
 // ws: pred_off | gt_off | seg_type | iou_off | cutoffs | slab_int [n_seg, 5, 101] | slab_ha [n_seg, 2, 101]
 struct WeWs {
-    size_t pred_off, gt_off, seg_type, iou_off, cutoffs, slab_int, slab_ha, total;
+    WsCarver c;
+    size_t pred_off, gt_off, seg_type, iou_off, cutoffs, slab_int, slab_ha;
+    explicit WeWs(int n_seg)
+        : pred_off(c.take((size_t)(n_seg + 1) * sizeof(int32_t))), gt_off(c.take((size_t)(n_seg + 1) * sizeof(int32_t))),
+          seg_type(c.take((size_t)n_seg * sizeof(int32_t))), iou_off(c.take((size_t)(n_seg + 1) * sizeof(long long))),
+          cutoffs(c.take((size_t)WE_CUT * sizeof(float))), slab_int(c.take((size_t)n_seg * WE_INT_ROWS * WE_CUT * sizeof(int32_t))),
+          slab_ha(c.take((size_t)n_seg * WE_HA_ROWS * WE_CUT * sizeof(double))) {}
 };
 
-static WeWs we_layout(int n_seg) {
-    WeWs w;
-    size_t at = 0;
-    auto take = [&](size_t bytes) {
-        const size_t here = at;
-        at += align_up(bytes, 256);
-        return here;
-    };
-    w.pred_off = take((size_t)(n_seg + 1) * sizeof(int32_t));
-    w.gt_off = take((size_t)(n_seg + 1) * sizeof(int32_t));
-    w.seg_type = take((size_t)n_seg * sizeof(int32_t));
-    w.iou_off = take((size_t)(n_seg + 1) * sizeof(long long));
-    w.cutoffs = take((size_t)WE_CUT * sizeof(float));
-    w.slab_int = take((size_t)n_seg * WE_INT_ROWS * WE_CUT * sizeof(int32_t));
-    w.slab_ha = take((size_t)n_seg * WE_HA_ROWS * WE_CUT * sizeof(double));
-    w.total = at;
-    return w;
-}
-
-// the CSR offsets of both sides and of the IoU blocks, read on the host before anything is launched
-static int we_check_offsets(const char* who, int n_pred, int n_gt, const int32_t* pred_off, const int32_t* gt_off, const long long* iou_off,
-                            int n_seg, long long n_pairs) {
+// the sizes, the CSR offsets of both sides (csr_check) and the IoU blocks, read on the host before anything is launched
+static int we_check_spans(const char* who, int n_pred, int n_gt, const int32_t* pred_off, const int32_t* gt_off, const long long* iou_off,
+                          int n_seg, long long n_pairs) {
     TODA_CHECK_ARG(n_pred >= 0 && n_gt >= 0 && n_seg >= 0 && n_pairs >= 0, "%s: negative size (n_pred %d, n_gt %d, n_seg %d, n_pairs %lld)", who,
                    n_pred, n_gt, n_seg, n_pairs);
     if (n_seg == 0) {
@@ -445,14 +389,11 @@ static int we_check_offsets(const char* who, int n_pred, int n_gt, const int32_t
         return TODA_OK;
     }
     TODA_CHECK_ARG(pred_off && gt_off && iou_off, "%s: null offsets", who);
-    TODA_CHECK_ARG(pred_off[0] == 0 && gt_off[0] == 0 && iou_off[0] == 0 && pred_off[n_seg] == n_pred && gt_off[n_seg] == n_gt &&
-                       iou_off[n_seg] == n_pairs,
-                   "%s: offsets must run from 0 to n_pred / n_gt / n_pairs", who);
+    if (csr_check(who, pred_off, n_seg, n_pred, WE_MAX_PRED, "predictions") != TODA_OK) return TODA_EINVAL;
+    if (csr_check(who, gt_off, n_seg, n_gt, WE_MAX_GT, "ground truths") != TODA_OK) return TODA_EINVAL;
+    TODA_CHECK_ARG(iou_off[0] == 0 && iou_off[n_seg] == n_pairs, "%s: the offsets of the IoU blocks must run from 0 to n_pairs", who);
     for (int s = 0; s < n_seg; ++s) {
         const int np = pred_off[s + 1] - pred_off[s], ng = gt_off[s + 1] - gt_off[s];
-        TODA_CHECK_ARG(np >= 0 && ng >= 0, "%s: offsets of segment %d descend", who, s);
-        TODA_CHECK_ARG(np <= WE_MAX_PRED, "%s: segment %d has %d predictions, at most %d are assigned", who, s, np, WE_MAX_PRED);
-        TODA_CHECK_ARG(ng <= WE_MAX_GT, "%s: segment %d has %d ground truths, at most %d are assigned", who, s, ng, WE_MAX_GT);
         TODA_CHECK_ARG(iou_off[s + 1] - iou_off[s] == (long long)np * ng, "%s: the IoU block of segment %d is not [%d, %d]", who, s, np, ng);
     }
     return TODA_OK;
@@ -464,24 +405,24 @@ using namespace toda;
 
 extern "C" size_t toda_waymo_eval_match_workspace_bytes(int n_seg) {
     if (n_seg < 1) return 0;
-    return we_layout(n_seg).total;
+    return WeWs(n_seg).c.at;
 }
 
 extern "C" int toda_waymo_eval_iou(const double* pred, int n_pred, const double* gt, int n_gt, const int32_t* pred_off_host,
                                    const int32_t* gt_off_host, const long long* iou_off_host, int n_seg, long long n_pairs, double* iou,
                                    void* ws, size_t ws_bytes, void* stream) {
-    if (we_check_offsets("waymo_eval_iou", n_pred, n_gt, pred_off_host, gt_off_host, iou_off_host, n_seg, n_pairs) != TODA_OK) return TODA_EINVAL;
+    if (we_check_spans("waymo_eval_iou", n_pred, n_gt, pred_off_host, gt_off_host, iou_off_host, n_seg, n_pairs) != TODA_OK) return TODA_EINVAL;
     if (n_seg == 0 || n_pairs == 0) return TODA_OK;
     TODA_CHECK_ARG(pred && gt && iou, "waymo_eval_iou: null boxes or output");
-    TODA_CHECK_ARG(ws && ws_bytes >= toda_waymo_eval_match_workspace_bytes(n_seg), "waymo_eval_iou: workspace too small");
+    const WeWs w(n_seg);
+    TODA_CHECK_ARG(ws && ws_bytes >= w.c.at, "waymo_eval_iou: workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    const WeWs w = we_layout(n_seg);
-    char* base = (char*)ws;
-    TODA_HIP(hipMemcpyAsync(base + w.pred_off, pred_off_host, (size_t)(n_seg + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    TODA_HIP(hipMemcpyAsync(base + w.gt_off, gt_off_host, (size_t)(n_seg + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    TODA_HIP(hipMemcpyAsync(base + w.iou_off, iou_off_host, (size_t)(n_seg + 1) * sizeof(long long), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(waymo_eval_iou_kernel, dim3(n_seg), dim3(WE_IOU_BLOCK), 0, s, pred, gt, (const int32_t*)(base + w.pred_off),
-                       (const int32_t*)(base + w.gt_off), (const long long*)(base + w.iou_off), n_pred, n_gt, iou);
+    const int32_t *pred_off, *gt_off;
+    const long long* iou_off;
+    TODA_HIP(stage(ws, w.pred_off, pred_off_host, n_seg + 1, s, &pred_off));
+    TODA_HIP(stage(ws, w.gt_off, gt_off_host, n_seg + 1, s, &gt_off));
+    TODA_HIP(stage(ws, w.iou_off, iou_off_host, n_seg + 1, s, &iou_off));
+    hipLaunchKernelGGL(waymo_eval_iou_kernel, dim3(n_seg), dim3(WE_IOU_BLOCK), 0, s, pred, gt, pred_off, gt_off, iou_off, n_pred, n_gt, iou);
     TODA_LAUNCH_CHECK();
     return TODA_OK;
 }
@@ -491,7 +432,7 @@ extern "C" int toda_waymo_eval_match(const double* iou, const float* pred_score,
                                      const int32_t* gt_off_host, const long long* iou_off_host, const int32_t* seg_type_host, int n_seg,
                                      long long n_pairs, const float* cutoffs_host, long long* tp, long long* fn, long long* fp,
                                      double* sum_ha, int32_t* match_dbg, void* ws, size_t ws_bytes, void* stream) {
-    if (we_check_offsets("waymo_eval_match", n_pred, n_gt, pred_off_host, gt_off_host, iou_off_host, n_seg, n_pairs) != TODA_OK) return TODA_EINVAL;
+    if (we_check_spans("waymo_eval_match", n_pred, n_gt, pred_off_host, gt_off_host, iou_off_host, n_seg, n_pairs) != TODA_OK) return TODA_EINVAL;
     TODA_CHECK_ARG(tp && fn && fp && sum_ha, "waymo_eval_match: null output");
     TODA_CHECK_ARG(cutoffs_host, "waymo_eval_match: null cutoffs");
     for (int k = 0; k < WE_CUT; ++k)
@@ -513,31 +454,24 @@ extern "C" int toda_waymo_eval_match(const double* iou, const float* pred_score,
     TODA_CHECK_ARG(n_pred == 0 || (pred_score && pred_heading), "waymo_eval_match: null scores or headings of the predictions");
     TODA_CHECK_ARG(n_gt == 0 || (gt_heading && gt_level), "waymo_eval_match: null headings or levels of the ground truths");
     TODA_CHECK_ARG(n_pairs == 0 || iou, "waymo_eval_match: null IoU blocks");
-    TODA_CHECK_ARG(ws && ws_bytes >= toda_waymo_eval_match_workspace_bytes(n_seg), "waymo_eval_match: workspace too small");
-    const WeWs w = we_layout(n_seg);
-    char* base = (char*)ws;
-    TODA_HIP(hipMemcpyAsync(base + w.pred_off, pred_off_host, (size_t)(n_seg + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    TODA_HIP(hipMemcpyAsync(base + w.gt_off, gt_off_host, (size_t)(n_seg + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    TODA_HIP(hipMemcpyAsync(base + w.seg_type, seg_type_host, (size_t)n_seg * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    TODA_HIP(hipMemcpyAsync(base + w.iou_off, iou_off_host, (size_t)(n_seg + 1) * sizeof(long long), hipMemcpyHostToDevice, s));
-    TODA_HIP(hipMemcpyAsync(base + w.cutoffs, cutoffs_host, (size_t)WE_CUT * sizeof(float), hipMemcpyHostToDevice, s));
+    const WeWs w(n_seg);
+    TODA_CHECK_ARG(ws && ws_bytes >= w.c.at, "waymo_eval_match: workspace too small");
     WeMatch p = {};
+    TODA_HIP(stage(ws, w.pred_off, pred_off_host, n_seg + 1, s, &p.pred_off));
+    TODA_HIP(stage(ws, w.gt_off, gt_off_host, n_seg + 1, s, &p.gt_off));
+    TODA_HIP(stage(ws, w.iou_off, iou_off_host, n_seg + 1, s, &p.iou_off));
+    TODA_HIP(stage(ws, w.seg_type, seg_type_host, n_seg, s, &p.seg_type));
+    TODA_HIP(stage(ws, w.cutoffs, cutoffs_host, WE_CUT, s, &p.cutoffs));
     p.iou = iou;
     p.score = pred_score;
     p.pred_heading = pred_heading;
     p.gt_heading = gt_heading;
     p.gt_level = gt_level;
-    p.pred_off = (const int32_t*)(base + w.pred_off);
-    p.gt_off = (const int32_t*)(base + w.gt_off);
-    p.iou_off = (const long long*)(base + w.iou_off);
-    p.seg_type = (const int32_t*)(base + w.seg_type);
-    p.cutoffs = (const float*)(base + w.cutoffs);
-    p.n_seg = n_seg;
     p.n_pred = n_pred;
     p.n_gt = n_gt;
-    int32_t* slab_int = (int32_t*)(base + w.slab_int);
-    double* slab_ha = (double*)(base + w.slab_ha);
-    hipLaunchKernelGGL(waymo_eval_match_kernel, dim3(n_seg), dim3(WE_WAVE), 0, s, p, slab_int, slab_ha, match_dbg);
+    int32_t* slab_int = (int32_t*)((char*)ws + w.slab_int);
+    double* slab_ha = (double*)((char*)ws + w.slab_ha);
+    hipLaunchKernelGGL(waymo_eval_match_kernel, dim3(n_seg), dim3(EVAL_WAVE), 0, s, p, slab_int, slab_ha, match_dbg);
     TODA_LAUNCH_CHECK();
     hipLaunchKernelGGL(waymo_eval_fold_kernel, dim3((WE_INT_ROWS + WE_HA_ROWS) * WE_CUT, WE_TYPES), dim3(WE_FOLD_BLOCK), 0, s,
                        (const int32_t*)slab_int, (const double*)slab_ha, p.seg_type, n_seg, tp, fn, fp, sum_ha);

@@ -1841,6 +1841,30 @@ def _eval_arg(t, dtype, what):
     return t
 
 
+def eval_upload(a, dtype, dev):
+    """A host array as a contiguous tensor of numpy dtype `dtype` on `dev`: how the evaluators hand their tables to the ops below."""
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
+
+
+def _eval_host(a, dtype, shape=None, what=None):
+    """A HOST array the launcher reads before it launches: contiguous, of numpy dtype `dtype`, of `shape` (None: any) or raise `what`."""
+    a = np.ascontiguousarray(a, dtype=dtype)
+    if shape is not None and a.shape != tuple(shape):
+        raise RuntimeError(what)
+    return a
+
+
+def _eval_call(name, ws_query, dev, *args, host_arrays=False):
+    """lib.<name>(*args, ws, ws_bytes, stream), checked, on a fresh byte workspace of the size the export ws_query[0] returns for the
+    arguments ws_query[1:]; host_arrays: the call read host arrays."""
+    lib = L.load()
+    ws_bytes = getattr(lib, ws_query[0])(*ws_query[1:])
+    ws = torch.empty((max(int(ws_bytes), 1),), dtype=torch.uint8, device=dev)
+    L.check(getattr(lib, name)(*args, L.ptr(ws), ws_bytes, L.stream()), name)
+    if host_arrays:
+        torch.cuda.current_stream().synchronize()       # the host arrays have been read once the copies into ws are done
+
+
 def eval_overlaps(box3d, bbox, box_off, query3d, query_bbox, query_off, out_off, n_pairs, metric, criterion=-1):
     """The KITTI evaluator's per-frame overlaps (toda_eval_overlaps): flat fp32 of n_pairs values, frame f's
     [n_box_f, n_query_f] block at out_off[f].  box3d / query3d [N, 7] = x, y, z, l, h, w, rotation_y (camera frame), bbox /
@@ -1874,18 +1898,14 @@ def _eval_match_common(overlaps, ov_off, det_off, gt_off, ign_det, ign_gt, score
 def eval_match_scores(overlaps, ov_off, det_off, gt_off, ign_det, ign_gt, score, min_overlap):
     """The evaluator's threshold-free matching pass (toda_eval_match_scores) -> (scores fp64 [n_gt], counts int32 [F]): the
     first counts[f] entries from gt_off[f] on are the scores of the detections matched to frame f's counted ground truths."""
-    lib = L.load()
     overlaps, ov_off, offs, score, n_frames, n_det, n_gt = _eval_match_common(overlaps, ov_off, det_off, gt_off, ign_det, ign_gt,
                                                                               score, "eval_match_scores")
     dev = ov_off.device
     scores_out = torch.empty((n_gt,), dtype=torch.float64, device=dev)
     counts = torch.zeros((max(n_frames, 0),), dtype=torch.int32, device=dev)
-    ws_bytes = lib.toda_eval_match_workspace_bytes(n_frames, 1, n_det)
-    ws = torch.empty((max(int(ws_bytes), 1),), dtype=torch.uint8, device=dev)
-    rc = lib.toda_eval_match_scores(L.ptr(overlaps), L.ptr(ov_off), L.ptr(offs[0]), L.ptr(offs[1]), L.ptr(offs[2]), L.ptr(offs[3]),
-                                    L.ptr(score), n_frames, n_det, float(min_overlap), L.ptr(scores_out), L.ptr(counts),
-                                    L.ptr(ws), ws_bytes, L.stream())
-    L.check(rc, "toda_eval_match_scores")
+    _eval_call("toda_eval_match_scores", ("toda_eval_match_workspace_bytes", n_frames, 1, n_det), dev, L.ptr(overlaps), L.ptr(ov_off),
+               L.ptr(offs[0]), L.ptr(offs[1]), L.ptr(offs[2]), L.ptr(offs[3]), L.ptr(score), n_frames, n_det, float(min_overlap),
+               L.ptr(scores_out), L.ptr(counts))
     return scores_out, counts
 
 
@@ -1893,7 +1913,6 @@ def eval_match(overlaps, ov_off, det_off, gt_off, ign_det, ign_gt, score, det_al
                thresholds, min_overlap, metric, compute_aos=False):
     """The evaluator's matching at every score threshold (toda_eval_match) -> pr fp64 [T, 4] = (tp, fp, fn, AOS similarity)
     summed over the frames in a fixed order.  det_bbox / dc_bbox / dc_off are read for metric 0, the alphas with compute_aos."""
-    lib = L.load()
     overlaps, ov_off, offs, score, n_frames, n_det, n_gt = _eval_match_common(overlaps, ov_off, det_off, gt_off, ign_det, ign_gt,
                                                                               score, "eval_match")
     f64 = [_eval_arg(t, torch.float64, "eval_match: alphas, image boxes and thresholds") for t in (det_alpha, gt_alpha, det_bbox, dc_bbox, thresholds)]
@@ -1901,13 +1920,10 @@ def eval_match(overlaps, ov_off, det_off, gt_off, ign_det, ign_gt, score, det_al
     dev = ov_off.device
     n_thresh = int(f64[4].numel())
     pr = torch.zeros((n_thresh, 4), dtype=torch.float64, device=dev)
-    ws_bytes = lib.toda_eval_match_workspace_bytes(n_frames, n_thresh, n_det)
-    ws = torch.empty((max(int(ws_bytes), 1),), dtype=torch.uint8, device=dev)
-    rc = lib.toda_eval_match(L.ptr(overlaps), L.ptr(ov_off), L.ptr(offs[0]), L.ptr(offs[1]), L.ptr(offs[2]), L.ptr(offs[3]),
-                             L.ptr(score), L.ptr(f64[0]), L.ptr(f64[1]), L.ptr(f64[2]), L.ptr(f64[3]), L.ptr(dc_off), n_frames,
-                             n_det, L.ptr(f64[4]), n_thresh, float(min_overlap), int(metric), int(bool(compute_aos)), L.ptr(pr),
-                             L.ptr(ws), ws_bytes, L.stream())
-    L.check(rc, "toda_eval_match")
+    _eval_call("toda_eval_match", ("toda_eval_match_workspace_bytes", n_frames, n_thresh, n_det), dev, L.ptr(overlaps), L.ptr(ov_off),
+               L.ptr(offs[0]), L.ptr(offs[1]), L.ptr(offs[2]), L.ptr(offs[3]), L.ptr(score), L.ptr(f64[0]), L.ptr(f64[1]), L.ptr(f64[2]),
+               L.ptr(f64[3]), L.ptr(dc_off), n_frames, n_det, L.ptr(f64[4]), n_thresh, float(min_overlap), int(metric),
+               int(bool(compute_aos)), L.ptr(pr))
     return pr
 
 
@@ -1940,28 +1956,22 @@ def nusc_eval_match(pred, score, pred_attr, gt, gt_attr, pred_off, gt_off, seg_c
     err fp64 [5, n_pred] at thresholds[tp_threshold]: trans, vel, scale, orient, attr, NaN where unmatched).  pred / gt fp64
     [., 8] = centre x y, yaw, velocity x y, dx dy dz in segment order; pred_off / gt_off / seg_cls are HOST int32 arrays (CSR
     offsets [n_seg + 1] and the class number of each segment)."""
-    lib = L.load()
     pred, score, gt = (_eval_arg(t, torch.float64, "nusc_eval_match: boxes and scores") for t in (pred, score, gt))
     pred_attr, gt_attr = (_eval_arg(t, torch.int32, "nusc_eval_match: attributes") for t in (pred_attr, gt_attr))
-    pred_off, gt_off, seg_cls = (np.ascontiguousarray(a, dtype=np.int32) for a in (pred_off, gt_off, seg_cls))
-    ths = np.ascontiguousarray(thresholds, dtype=np.float64)
+    seg_cls = _eval_host(seg_cls, np.int32)
     n_pred, n_gt, n_seg = int(pred.shape[0]), int(gt.shape[0]), int(seg_cls.shape[0])
     if pred.dim() != 2 or pred.shape[1] != 8 or gt.dim() != 2 or gt.shape[1] != 8:
         raise RuntimeError("nusc_eval_match: pred and gt must be [., 8]")
     if score.numel() != n_pred or pred_attr.numel() != n_pred or gt_attr.numel() != n_gt:
         raise RuntimeError("nusc_eval_match: one score and one attribute per prediction, one attribute per ground truth")
-    if pred_off.shape != (n_seg + 1,) or gt_off.shape != (n_seg + 1,) or ths.shape != (4,):
-        raise RuntimeError("nusc_eval_match: offsets must be [n_seg + 1], and there are four thresholds")
+    pred_off, gt_off, ths = (_eval_host(a, dt, shape, "nusc_eval_match: offsets must be [n_seg + 1], and there are four thresholds")
+                             for a, dt, shape in ((pred_off, np.int32, (n_seg + 1,)), (gt_off, np.int32, (n_seg + 1,)), (thresholds, np.float64, (4,))))
     dev = pred.device
     match = torch.empty((4, n_pred), dtype=torch.int32, device=dev)
     err = torch.empty((5, n_pred), dtype=torch.float64, device=dev)
-    ws_bytes = lib.toda_nusc_eval_match_workspace_bytes(n_seg)
-    ws = torch.empty((max(int(ws_bytes), 1),), dtype=torch.uint8, device=dev)
-    rc = lib.toda_nusc_eval_match(L.ptr(pred), L.ptr(score), L.ptr(pred_attr), n_pred, L.ptr(gt), L.ptr(gt_attr), n_gt,
-                                  pred_off.ctypes.data, gt_off.ctypes.data, seg_cls.ctypes.data, n_seg, ths.ctypes.data,
-                                  int(tp_threshold), L.ptr(match), L.ptr(err), L.ptr(ws), ws_bytes, L.stream())
-    L.check(rc, "toda_nusc_eval_match")
-    torch.cuda.current_stream().synchronize()           # the host offsets have been read once the copies into ws are done
+    _eval_call("toda_nusc_eval_match", ("toda_nusc_eval_match_workspace_bytes", n_seg), dev, L.ptr(pred), L.ptr(score), L.ptr(pred_attr),
+               n_pred, L.ptr(gt), L.ptr(gt_attr), n_gt, pred_off.ctypes.data, gt_off.ctypes.data, seg_cls.ctypes.data, n_seg,
+               ths.ctypes.data, int(tp_threshold), L.ptr(match), L.ptr(err), host_arrays=True)
     return match, err
 
 
@@ -1975,7 +1985,7 @@ def waymo_score_cutoffs():
 
 
 def _waymo_offsets(pred_off, gt_off, who):
-    pred_off, gt_off = (np.ascontiguousarray(a, dtype=np.int32) for a in (pred_off, gt_off))
+    pred_off, gt_off = (_eval_host(a, np.int32) for a in (pred_off, gt_off))
     if pred_off.ndim != 1 or pred_off.shape != gt_off.shape or pred_off.shape[0] < 1:
         raise RuntimeError(f"{who}: pred_off and gt_off must be [n_seg + 1]")
     iou_off = np.zeros(pred_off.shape[0], dtype=np.int64)
@@ -1987,19 +1997,15 @@ def waymo_eval_iou(pred, gt, pred_off, gt_off):
     """The Waymo metric's 7-DOF IoU of every same-segment pair (toda_waymo_eval_iou) -> flat fp64; segment s's [n_pred_s, n_gt_s]
     block starts at sum over earlier segments of n_pred * n_gt.  pred / gt fp64 [., 7] = x y z dx dy dz heading in segment order;
     pred_off / gt_off are HOST int32 CSR offsets [n_seg + 1]."""
-    lib = L.load()
     pred, gt = (_eval_arg(t, torch.float64, "waymo_eval_iou: boxes") for t in (pred, gt))
     if pred.dim() != 2 or pred.shape[1] != 7 or gt.dim() != 2 or gt.shape[1] != 7:
         raise RuntimeError("waymo_eval_iou: pred and gt must be [., 7]")
     pred_off, gt_off, iou_off = _waymo_offsets(pred_off, gt_off, "waymo_eval_iou")
     n_seg, n_pairs = int(pred_off.shape[0]) - 1, int(iou_off[-1])
     iou = torch.empty((n_pairs,), dtype=torch.float64, device=pred.device)
-    ws_bytes = lib.toda_waymo_eval_match_workspace_bytes(n_seg)
-    ws = torch.empty((max(int(ws_bytes), 1),), dtype=torch.uint8, device=pred.device)
-    rc = lib.toda_waymo_eval_iou(L.ptr(pred), int(pred.shape[0]), L.ptr(gt), int(gt.shape[0]), pred_off.ctypes.data, gt_off.ctypes.data,
-                                 iou_off.ctypes.data, n_seg, n_pairs, L.ptr(iou), L.ptr(ws), ws_bytes, L.stream())
-    L.check(rc, "toda_waymo_eval_iou")
-    torch.cuda.current_stream().synchronize()           # the host offsets have been read once the copies into ws are done
+    _eval_call("toda_waymo_eval_iou", ("toda_waymo_eval_match_workspace_bytes", n_seg), pred.device, L.ptr(pred), int(pred.shape[0]),
+               L.ptr(gt), int(gt.shape[0]), pred_off.ctypes.data, gt_off.ctypes.data, iou_off.ctypes.data, n_seg, n_pairs, L.ptr(iou),
+               host_arrays=True)
     return iou
 
 
@@ -2009,17 +2015,14 @@ def waymo_eval_match(iou, score, pred_heading, gt_heading, gt_level, pred_off, g
     waymo_eval_iou lays it out; score fp32 [n_pred]; headings fp64; gt_level int32 [n_gt] (the difficulty); pred_off / gt_off /
     seg_type (1 Vehicle, 2 Pedestrian, 3 Sign, 4 Cyclist) are HOST int32 arrays.  debug: also the match table, the row of the
     ground truth each prediction is assigned to at each cutoff, -1 when unmatched or inactive."""
-    lib = L.load()
     iou, pred_heading, gt_heading = (_eval_arg(t, torch.float64, "waymo_eval_match: IoU and headings") for t in (iou, pred_heading, gt_heading))
     score = _eval_arg(score, torch.float32, "waymo_eval_match: score")
     gt_level = _eval_arg(gt_level, torch.int32, "waymo_eval_match: gt_level")
     pred_off, gt_off, iou_off = _waymo_offsets(pred_off, gt_off, "waymo_eval_match")
-    seg_type = np.ascontiguousarray(seg_type, dtype=np.int32)
-    cuts = np.ascontiguousarray(waymo_score_cutoffs() if cutoffs is None else cutoffs, dtype=np.float32)
     n_seg, n_pairs = int(pred_off.shape[0]) - 1, int(iou_off[-1])
     n_pred, n_gt = int(score.numel()), int(gt_level.numel())
-    if seg_type.shape != (n_seg,) or cuts.shape != (WAYMO_CUTOFFS,):
-        raise RuntimeError(f"waymo_eval_match: one type per segment and {WAYMO_CUTOFFS} cutoffs")
+    seg_type, cuts = (_eval_host(a, dt, shape, f"waymo_eval_match: one type per segment and {WAYMO_CUTOFFS} cutoffs") for a, dt, shape in
+                      ((seg_type, np.int32, (n_seg,)), (waymo_score_cutoffs() if cutoffs is None else cutoffs, np.float32, (WAYMO_CUTOFFS,))))
     if pred_heading.numel() != n_pred or gt_heading.numel() != n_gt or iou.numel() != n_pairs:
         raise RuntimeError("waymo_eval_match: one heading per box, and the IoU blocks of the offsets")
     dev = score.device
@@ -2028,14 +2031,10 @@ def waymo_eval_match(iou, score, pred_heading, gt_heading, gt_level, pred_off, g
     fp = torch.empty((4, WAYMO_CUTOFFS), dtype=torch.int64, device=dev)
     sum_ha = torch.empty((4, 2, WAYMO_CUTOFFS), dtype=torch.float64, device=dev)
     match = torch.empty((WAYMO_CUTOFFS, n_pred), dtype=torch.int32, device=dev) if debug else None
-    ws_bytes = lib.toda_waymo_eval_match_workspace_bytes(n_seg)
-    ws = torch.empty((max(int(ws_bytes), 1),), dtype=torch.uint8, device=dev)
-    rc = lib.toda_waymo_eval_match(L.ptr(iou), L.ptr(score), L.ptr(pred_heading), n_pred, L.ptr(gt_heading), L.ptr(gt_level), n_gt,
-                                   pred_off.ctypes.data, gt_off.ctypes.data, iou_off.ctypes.data, seg_type.ctypes.data, n_seg, n_pairs,
-                                   cuts.ctypes.data, L.ptr(tp), L.ptr(fn), L.ptr(fp), L.ptr(sum_ha), L.ptr(match), L.ptr(ws), ws_bytes,
-                                   L.stream())
-    L.check(rc, "toda_waymo_eval_match")
-    torch.cuda.current_stream().synchronize()           # the host arrays have been read once the copies into ws are done
+    _eval_call("toda_waymo_eval_match", ("toda_waymo_eval_match_workspace_bytes", n_seg), dev, L.ptr(iou), L.ptr(score), L.ptr(pred_heading),
+               n_pred, L.ptr(gt_heading), L.ptr(gt_level), n_gt, pred_off.ctypes.data, gt_off.ctypes.data, iou_off.ctypes.data,
+               seg_type.ctypes.data, n_seg, n_pairs, cuts.ctypes.data, L.ptr(tp), L.ptr(fn), L.ptr(fp), L.ptr(sum_ha), L.ptr(match),
+               host_arrays=True)
     return tp, fn, fp, sum_ha, match
 
 

@@ -11,6 +11,7 @@ nuscenes`, which keeps raising ImportError here); the devkit walks every predict
 The ground truth comes from the info pickles.  They keep a ground truth's LiDAR-frame yaw only, so its global yaw is rebuilt
 from the rotation of G = inv(car_from_global) . inv(ref_from_car); bike racks come from the tables, because a rack without a
 LiDAR point is absent from the infos."""
+import functools
 import json
 import time
 from pathlib import Path
@@ -291,7 +292,7 @@ def match_on_device(pred, score, pred_attr, gt, gt_attr, pred_off, gt_off, seg_c
 
     from .... import ops
     dev = torch.device("cuda")
-    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)     # noqa: E731
+    up = functools.partial(ops.eval_upload, dev=dev)
     match, err = ops.nusc_eval_match(up(pred, np.float64), up(score, np.float64), up(pred_attr, np.int32), up(gt, np.float64),
                                      up(gt_attr, np.int32), pred_off, gt_off, seg_cls, DIST_THS, DIST_THS.index(DIST_TH_TP))
     return match.cpu().numpy(), err.cpu().numpy()

@@ -15,6 +15,7 @@ route of the tests and the baseline of tools/bench_waymo_eval.py.
 Agreement with the numbers of the official C++ metric is unmeasured: that tool is on no machine this project runs on.  Its
 handling of recall gaps wider than 0.05 (`desired_recall_delta`) is not restated, and the no-label-zone flag is zero, as in the
 reference."""
+import functools
 import warnings
 
 import numpy as np
@@ -137,9 +138,9 @@ def counts_device(seg, max_segments=MAX_SEGMENTS_PER_LAUNCH):
 
     from .... import ops
     dev = torch.device("cuda")
+    up = functools.partial(ops.eval_upload, dev=dev)
     tp, fn, fp, ha = empty_counts()
     for part in launch_slices(seg, max_segments):
-        up = lambda a, dtype: torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)             # noqa: E731
         pred, gt = up(part["pred_boxes"], np.float64), up(part["gt_boxes"], np.float64)
         iou = ops.waymo_eval_iou(pred, gt, part["pred_off"], part["gt_off"])
         out = ops.waymo_eval_match(iou, up(part["pred_score"], np.float32), pred[:, 6].contiguous(), gt[:, 6].contiguous(),

@@ -9,6 +9,7 @@ evaluate() call (tables, both kernels, orders, curves, both JSON files), and the
 class) one vectorised distance matrix and the greedy walk over the predictions, for the first --host-samples samples, checked
 against the kernel's match table."""
 import argparse
+import functools
 import json
 import os
 import tempfile
@@ -123,7 +124,7 @@ def main(argv=None):
             walls.append(time.perf_counter() - t0)
         pred, score, p_attr, gt, g_attr, p_off, g_off, seg_cls = held["args"]
         dev = torch.device("cuda")
-        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)      # noqa: E731
+        up = functools.partial(ops.eval_upload, dev=dev)
         d_args = (up(pred, np.float64), up(score, np.float64), up(p_attr, np.int32), up(gt, np.float64), up(g_attr, np.int32))
         rows = up(np.random.default_rng(0).uniform(-40, 40, (len(pred) + len(gt), 10)), np.float64)
         sample = up(np.random.default_rng(0).integers(0, len(infos), len(pred) + len(gt)), np.int32)

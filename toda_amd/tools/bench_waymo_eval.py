@@ -10,6 +10,7 @@ match launch (device events around the calls, summed over the launches of at mos
 101 cutoffs of every segment - on the IoU blocks of the first --host-frames frames, scaled to all frames.  No ratio to the official
 C++ metric exists: that tool is on no machine this project runs on."""
 import argparse
+import functools
 import json
 import os
 import time
@@ -53,9 +54,9 @@ def device_pass(seg):
     from .. import ops
     dev = torch.device("cuda")
     iou_ms = match_ms = 0.0
+    up = functools.partial(ops.eval_upload, dev=dev)
     counts, first = ev.empty_counts(), None
     for part in ev.launch_slices(seg, ev.MAX_SEGMENTS_PER_LAUNCH):
-        up = lambda a, dtype: torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)             # noqa: E731
         pred, gt, score, level = up(part["pred_boxes"], np.float64), up(part["gt_boxes"], np.float64), up(part["pred_score"], np.float32), up(part["gt_level"], np.int32)
         ph, gh = pred[:, 6].contiguous(), gt[:, 6].contiguous()
         e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
