@@ -977,6 +977,25 @@ int toda_waymo_eval_match(const double* iou, const float* pred_score, const doub
                           long long n_pairs, const float* cutoffs_host, long long* tp, long long* fn, long long* fp,
                           double* sum_ha, int32_t* match_dbg, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The consistency term of the stage-2 step (reference pcdet/models/__init__.py get_consistency_loss): mutual
+ * nearest-centre matching between the boxes of the adversarial and the original pass, and both loss terms, for a whole batch.
+ * adv [batch, na, cols] and org [batch, no, cols] fp32 rows x y z dx dy dz ..., cols >= 6; adv_sel [batch, na] and org_sel
+ * [batch, no] one byte per row, non-zero = the row takes part.  Unselected rows are never read.
+ *   d2(i, j) = ((ax - ox)^2 + (ay - oy)^2) + (az - oz)^2 in fp32, in this order, no contraction.
+ *   best(i) = min over the selected j, p(i) = the smallest j that attains it; a NaN distance counts as smaller than every
+ *   number (a row that meets one has best = NaN and no partner); no selected j: best = +inf.  i is matched iff
+ *   best(i) < match_dist2, strictly.  The same for every selected j over the selected i.
+ *   centre_sum = sum over matched i, c < 3 of |a[i, c] - o[p(i), c]| + the same over matched j; size_sum: (. - .)^2 over
+ *   columns 3..5.  n = max(1, selected adv + selected org).
+ * out [2 + 4 * batch]: sum_b (centre_sum_b / n_b) / batch, sum_b (size_sum_b / n_b) / batch, then per sample centre_sum,
+ * size_sum, selected, matched (counts as fp32).  No float atomics, every sum folded in a fixed order: two runs give the same
+ * bits.  Two launches.  ws: toda_consistency_workspace_bytes(batch, na, no) bytes.
+ * ---------------------------------------------------------------------- */
+size_t toda_consistency_workspace_bytes(int batch, int na, int no);
+int toda_consistency_loss(const float* adv, const uint8_t* adv_sel, int na, const float* org, const uint8_t* org_sel, int no,
+                          int batch, int cols, float match_dist2, float* out, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

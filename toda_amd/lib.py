@@ -175,6 +175,8 @@ SIGNATURES = {
     "toda_waymo_eval_match_workspace_bytes": (_sz, [_i]),
     "toda_waymo_eval_iou": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, C.c_longlong, _vp, _vp, _sz, _vp]),
     "toda_waymo_eval_match": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, C.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "toda_consistency_workspace_bytes": (_sz, [_i, _i, _i]),
+    "toda_consistency_loss": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, C.c_float, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -2629,6 +2629,38 @@ def adv_edit(points, boxes, op, frac, seed, keys, grads, voxel_cfg, eps, cap_row
     return buf.finish(), counts
 
 
+CONSISTENCY_MATCH_DIST2 = 1.0          # reference get_consistency_loss: a partner counts below 1 m^2 of squared centre distance
+
+
+def consistency_match(adv, adv_sel, org, org_sel, match_dist2=CONSISTENCY_MATCH_DIST2):
+    """Mutual nearest-centre matching and both consistency terms of a batch (C ABI: toda_consistency_loss).  adv [B, Na, cols],
+    org [B, No, cols] fp32 device boxes (x y z dx dy dz ...), adv_sel [B, Na] and org_sel [B, No] bool / uint8: the rows that
+    take part (the others are never read).  Returns (centre, size, per_sample): two 0-dim fp32 tensors, the batch means of the
+    per-sample terms, and per_sample [B, 4] = centre_sum, size_sum, selected, matched.  No gradient, no host synchronisation."""
+    lib = L.load()
+    if adv.dim() != 3 or org.dim() != 3 or adv.shape[0] != org.shape[0] or adv.shape[2] != org.shape[2]:
+        raise RuntimeError(f"consistency_match: adv [B, Na, cols] and org [B, No, cols], got {tuple(adv.shape)} and {tuple(org.shape)}")
+    if adv.dtype != torch.float32 or org.dtype != torch.float32:
+        raise RuntimeError("consistency_match: boxes must be float32")
+    batch, na, cols = adv.shape
+    no = org.shape[1]
+    sels = []
+    for sel, n, who in ((adv_sel, na, "adv_sel"), (org_sel, no, "org_sel")):
+        if tuple(sel.shape) != (batch, n) or sel.dtype not in (torch.bool, torch.uint8):
+            raise RuntimeError(f"consistency_match: {who} must be bool or uint8 [{batch}, {n}], got {sel.dtype} {tuple(sel.shape)}")
+        sel = sel.contiguous()
+        sels.append(sel.view(torch.uint8) if sel.dtype == torch.bool else sel)
+    adv, org = adv.detach().contiguous(), org.detach().contiguous()
+    out = torch.empty((2 + 4 * batch,), dtype=torch.float32, device=adv.device)
+    ws_bytes = lib.toda_consistency_workspace_bytes(batch, na, no)
+    ws = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=adv.device)
+    rc = lib.toda_consistency_loss(L.ptr(adv) if na else None, L.ptr(sels[0]) if na else None, na, L.ptr(org) if no else None,
+                                   L.ptr(sels[1]) if no else None, no, batch, cols, float(match_dist2), L.ptr(out), L.ptr(ws), ws_bytes,
+                                   L.stream())
+    L.check(rc, "toda_consistency_loss")
+    return out[0], out[1], out[2:].view(batch, 4)
+
+
 def points_polar_cell(points, phase, yaw_edges, dis_edges, dis_lo, dis_hi, n_dev=None):
     ye, de = L.host_f64(yaw_edges), L.host_f64(dis_edges)
     return _row_pass("toda_points_polar_cell", points, n_dev, -1, float(phase), L.hptr(ye), len(yaw_edges) - 1, L.hptr(de),

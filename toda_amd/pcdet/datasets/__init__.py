@@ -11,6 +11,7 @@ from torch.utils.data import DistributedSampler as _DistributedSampler
 from ..utils import common_utils
 from .dataset import DatasetTemplate
 from .kitti.kitti_dataset import KittiDataset
+from .kitti.kitti_mixup_adv_dataset import KittiMixUpAdvDataset
 from .nuscenes.nuscenes_dataset import NuScenesDataset
 from .nuscenes.nuscenes_mixup_adv_dataset import NuScenesMixUpAdvDataset
 from .synthetic import SyntheticLidarDataset, SyntheticPairDataset
@@ -21,6 +22,7 @@ from .waymo.waymo_dataset import WaymoDataset
 __all__ = {
     "DatasetTemplate": DatasetTemplate,
     "KittiDataset": KittiDataset,
+    "KittiMixUpAdvDataset": KittiMixUpAdvDataset,
     "NuScenesDataset": NuScenesDataset,
     "NuScenesMixUpAdvDataset": NuScenesMixUpAdvDataset,
     "WaymoDataset": WaymoDataset,

@@ -178,6 +178,11 @@ class KittiDataset(DatasetTemplate):
         counts[:k] = torch.bincount(owner[owner >= 0].long(), minlength=k).cpu().numpy()
         return counts
 
+    def dump_infos(self, path):
+        """The label-free view of the infos (no `annos`): what tools/generate_pseudo_labels fills with a teacher's detections."""
+        with open(path, "wb") as f:
+            pickle.dump([{k: v for k, v in info.items() if k != "annos"} for info in self.kitti_infos], f)
+
     # ---- GT database: the frames of an infos pickle through augmentor/database_sampler.create_groundtruth_database
     def create_groundtruth_database(self, info_path=None, used_classes=None, split="train"):
         from ..augmentor.database_sampler import create_groundtruth_database

@@ -19,8 +19,8 @@ Config keys (as in the reference YAMLs, e.g. tools/cfgs/stage1_targetmix/*.yaml)
 WaymoNusMixDataset is the dataset those YAMLs name (WaymoNusPolarMixDataset / ...CutMix... / ...LaserMix...: one class here,
 MIX_TYPE decides): source frames from a WaymoDataset, target frames from a NuScenesDataset, both read from disk.  Not built:
 DATA_CONFIG_TEST (evaluate through tools.test on a plain NuScenesDataset yaml).  Of the stage-2 real mixup datasets,
-NuScenesMixUpAdvDataset is built (nuscenes/nuscenes_mixup_adv_dataset.py); KittiMixUpAdvDataset and the non-adversarial
-NuScenesMixUpDataset are not.
+NuScenesMixUpAdvDataset (nuscenes/nuscenes_mixup_adv_dataset.py) and KittiMixUpAdvDataset (kitti/kitti_mixup_adv_dataset.py) are
+built; the non-adversarial NuScenesMixUpDataset is not.
 """
 import numpy as np
 import torch

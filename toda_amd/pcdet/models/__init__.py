@@ -425,9 +425,86 @@ def filter_boxes_centerpoint(batch_dict, model):
     return out
 
 
+@torch.no_grad()
+def filter_boxes_secondiou(batch_dict, model):
+    """NMS-ed boxes of a SECOND-IoU training forward (reference :262-314).  In training SECONDHead leaves batch_cls_preds /
+    batch_box_preds alone, so these are the anchor head's dense predictions: per sample sigmoid (unless already normalised), the
+    best class score, class_agnostic_nms under MODEL.POST_PROCESSING.  The recall record the reference computes here is thrown
+    away there and is not built.  The lists are unpadded: their lengths are host-known shapes after the NMS."""
+    from .model_utils.model_nms_utils import class_agnostic_nms
+
+    net = model.module if hasattr(model, "module") and not hasattr(model, "dense_head") else model
+    net = getattr(net, "onepass", net)
+    post = net.model_cfg.POST_PROCESSING
+    out = []
+    for index in range(int(batch_dict["batch_size"])):
+        if batch_dict.get("batch_index", None) is not None:
+            assert batch_dict["batch_cls_preds"].dim() == 2
+            pick = batch_dict["batch_index"] == index
+        else:
+            assert batch_dict["batch_cls_preds"].dim() == 3
+            pick = index
+        box_preds = batch_dict["batch_box_preds"][pick].detach()
+        scores = batch_dict["batch_cls_preds"][pick].detach()
+        if not batch_dict["cls_preds_normalized"]:
+            scores = torch.sigmoid(scores)
+        scores, _ = torch.max(scores, dim=-1)
+        selected, selected_scores = class_agnostic_nms(box_scores=scores, box_preds=box_preds, nms_config=post.NMS_CONFIG,
+                                                       score_thresh=post.SCORE_THRESH)
+        out.append({"pred_boxes": box_preds[selected], "pred_scores": selected_scores})
+    return out
+
+
+def consistency_filter(batch_dict, net):
+    """The box filter of the consistency step for what the detector's forward left in the batch dict."""
+    if "pred_dicts" in batch_dict:
+        return filter_boxes_centerpoint
+    if "batch_box_preds" in batch_dict and getattr(net, "roi_head", None) is not None:
+        return filter_boxes_secondiou
+    raise NotImplementedError(f"the consistency step knows CenterPoint (pred_dicts) and SECOND-IoU (batch_box_preds with a roi_head), "
+                              f"not {type(net).__name__}")
+
+
+def _consistency_batch(items, cols, use_mask):
+    """(boxes [B, n, cols], selection bytes [B, n]) of the per-sample box lists of one pass, on their device.  Lists of one length are
+    stacked; others are padded to the longest, the selection coming from the lengths (host-known shapes).  No read-back."""
+    boxes = [it["pred_boxes"].detach()[:, :cols] for it in items]
+    lens = [int(b.shape[0]) for b in boxes]
+    n, dev = max(lens), boxes[0].device
+    if min(lens) == n:
+        data = torch.stack(boxes)
+        sel = torch.stack([it["mask"] for it in items]) if use_mask else torch.ones((len(items), n), dtype=torch.uint8, device=dev)
+        return data, sel
+    data = boxes[0].new_zeros((len(items), n, cols))
+    sel = torch.zeros((len(items), n), dtype=torch.bool if use_mask else torch.uint8, device=dev)
+    for k, (b, m) in enumerate(zip(boxes, lens)):
+        data[k, :m] = b
+        sel[k, :m] = items[k]["mask"] if use_mask else 1
+    return data, sel
+
+
 def get_consistency_loss(adv_boxes, org_boxes):
-    """Nearest-centre matching (< 1 m^2) between the two passes; L1 on centres, MSE on sizes.  The
-    reference detaches both box sets (:229-230), so this term carries no gradient; kept as is."""
+    """Nearest-centre matching (< 1 m^2) between the two passes; L1 on centres, MSE on sizes.  The reference detaches both box sets
+    (:229-230), so this term carries no gradient.  Device lists go through one kernel call for the whole batch
+    (ops.consistency_match); host lists through the torch forms below, which are also the tests' reference."""
+    adv_boxes, org_boxes = list(adv_boxes), list(org_boxes)
+    if not adv_boxes or not org_boxes or not adv_boxes[0]["pred_boxes"].is_cuda:
+        return _consistency_loss_torch(adv_boxes, org_boxes)
+    from ... import ops
+
+    batch = min(len(adv_boxes), len(org_boxes))
+    adv_boxes, org_boxes = adv_boxes[:batch], org_boxes[:batch]
+    use_mask = all("mask" in a and "mask" in o for a, o in zip(adv_boxes, org_boxes))
+    cols = min(min(int(a["pred_boxes"].shape[1]) for a in adv_boxes), min(int(o["pred_boxes"].shape[1]) for o in org_boxes))
+    a, a_sel = _consistency_batch(adv_boxes, cols, use_mask)
+    o, o_sel = _consistency_batch(org_boxes, cols, use_mask)
+    centre, size, _ = ops.consistency_match(a, a_sel, o, o_sel)
+    return centre, size
+
+
+def _consistency_loss_torch(adv_boxes, org_boxes):
+    """The torch composition of get_consistency_loss: the padded form (lists with `mask`) and the unpadded form.  What host
+    tensors take, and the baseline the kernel route is tested and timed against on device tensors."""
     import torch.nn.functional as F
 
     centre_terms, size_terms, norm = [], [], 0
@@ -504,8 +581,9 @@ def model_fn_decorator_cl():
         finally:
             net.return_batch_dict = False
         loss_adv, loss_org = adv_ret["loss"].mean(), org_ret["loss"].mean()
-        adv_boxes = filter_boxes_centerpoint(adv_b, net)
-        org_boxes = reverse_transform(filter_boxes_centerpoint(org_b, net), org_b)
+        filter_boxes = consistency_filter(adv_b, net)
+        adv_boxes = filter_boxes(adv_b, net)
+        org_boxes = reverse_transform(filter_boxes(org_b, net), org_b)
         centre_loss, size_loss = get_consistency_loss(adv_boxes, org_boxes)
         loss = loss_adv + loss_org + 0.1 * (centre_loss + size_loss)
         net.update_global_step()

@@ -19,6 +19,9 @@ class SECONDNetIoU(Detector3DTemplate):
             batch_dict = module(batch_dict)
         if self.training:
             loss, tb_dict, disp_dict = self.get_training_loss()
+            if getattr(self, "return_batch_dict", False):
+                # the stage-2 consistency step filters the dense predictions itself (models.filter_boxes_secondiou)
+                return batch_dict, {"loss": loss}, tb_dict, disp_dict
             return {"loss": loss}, tb_dict, disp_dict
         return self.post_processing(batch_dict)
 

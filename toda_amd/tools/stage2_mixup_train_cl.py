@@ -6,6 +6,8 @@ the loop below is written from model_fn_decorator_cl, pcdet/models/__init__.py:8
     python -m toda_amd.tools.stage2_mixup_train_cl --cfg_file toda_amd/tools/cfgs/models/toda_stage1_centerpoint_res.yaml
     python -m toda_amd.tools.stage2_mixup_train_cl --cfg_file toda_amd/tools/cfgs/models/toda_stage2_nus_advmix_real.yaml \
         --pretrained_model <stage-1 ckpt> --pseudo_info_path <score_..._infos.pkl of generate_pseudo_labels --perturb>
+    python -m toda_amd.tools.stage2_mixup_train_cl --cfg_file toda_amd/tools/cfgs/models/toda_stage2_kitti_advmix_real.yaml \
+        --pretrained_model <stage-1 SECOND-IoU ckpt> --pseudo_info_path <score_..._infos.pkl>
 
 Both passes run inside one DistModel.forward so DDP issues one gradient all-reduce per step."""
 import os
@@ -76,7 +78,7 @@ def main(argv=None):
     epochs = cfg.OPTIMIZATION.NUM_EPOCHS if args.epochs is None else args.epochs
     logger = common_utils.create_logger(None, rank=cfg.LOCAL_RANK)
     # DATA_CONFIG.DATASET names a pair dataset (class attribute is_pair_dataset - SyntheticMixupPairDataset and, on frames read
-    # from disk, NuScenesMixUpAdvDataset: MixUp + adversarial frames, the TODA recipe); configs written for the single-frame
+    # from disk, NuScenesMixUpAdvDataset and KittiMixUpAdvDataset: MixUp + adversarial frames, the TODA recipe); configs written for the single-frame
     # datasets fall back to the plain (adv, org) pair of one frame
     cls = dataset_registry.__all__.get(cfg.DATA_CONFIG.DATASET, SyntheticPairDataset)
     if not getattr(cls, "is_pair_dataset", False):
