@@ -1,6 +1,7 @@
 """Dataset registry and dataloader builder (reference pcdet/datasets/__init__.py:25-97).  KittiDataset reads the KITTI
-object benchmark, NuScenesDataset the nuScenes sweeps and WaymoDataset the processed Waymo frames from disk, and
-WaymoNusMixDataset mixes the last two for TODA stage 1; the readers of the other real datasets (Lyft / ...) are out of scope,
+object benchmark, NuScenesDataset the nuScenes sweeps and WaymoDataset the processed Waymo frames from disk;
+WaymoNusMixDataset (Waymo -> nuScenes) and NusKittiMixDataset (nuScenes -> KITTI) mix two of them for TODA stage 1, each under
+the reference's per-mix names; the readers of the other real datasets (Lyft / ...) are out of scope,
 their shapes come from the synthetic datasets, which expose the same attributes and the same collate contract."""
 from functools import partial
 
@@ -16,7 +17,7 @@ from .nuscenes.nuscenes_dataset import NuScenesDataset
 from .nuscenes.nuscenes_mixup_adv_dataset import NuScenesMixUpAdvDataset
 from .synthetic import SyntheticLidarDataset, SyntheticPairDataset
 from .mixup_dataset import SyntheticMixupPairDataset
-from .two_dataset import SyntheticMixDataset, WaymoNusMixDataset
+from .two_dataset import NusKittiMixDataset, SyntheticMixDataset, WaymoNusMixDataset
 from .waymo.waymo_dataset import WaymoDataset
 
 __all__ = {
@@ -30,6 +31,9 @@ __all__ = {
     "WaymoNusPolarMixDataset": WaymoNusMixDataset,           # the reference's three names: MIX_TYPE decides which mix runs
     "WaymoNusCutMixDataset": WaymoNusMixDataset,
     "WaymoNusLaserMixDataset": WaymoNusMixDataset,
+    "NusKittiMixDataset": NusKittiMixDataset,
+    "NusKittiPolarMixDataset": NusKittiMixDataset,
+    "NusKittiCutMixDataset": NusKittiMixDataset,
     "SyntheticLidarDataset": SyntheticLidarDataset,
     "SyntheticPairDataset": SyntheticPairDataset,
     "SyntheticMixDataset": SyntheticMixDataset,

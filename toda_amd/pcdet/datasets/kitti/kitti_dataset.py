@@ -9,7 +9,8 @@ MI355X layout: the frame's points go file -> one H2D copy -> camera field-of-vie
 csrc/kitti_frame.hip) -> stable compaction (ops.RowBuffer) -> SHIFT_COOR (a tensor add) and then, still on the device, the
 range mask, the shuffle and the voxeliser of the data processor.  With FOV_POINTS_ONLY the samples are CUDA tensors
 (`on_device`): build_dataloader then runs the dataset in the training process (num_workers = 0), no worker process opens the
-GPU.  Without it the points stay numpy and reach the device with the batch, as SyntheticLidarDataset's do.  The info
+GPU.  Without it the points stay numpy and reach the device with the batch, as SyntheticLidarDataset's do; raw_frame(device=True),
+the frame before prepare_data that NusKittiMixDataset mixes, uploads them in either setting.  The info
 builder counts the points of every gt box on the device as well (points_in_boxes mode 2 + bincount) where the reference
 runs one Delaunay hull test per box.  Label, calibration and box arithmetic are host numpy.
 
@@ -245,14 +246,16 @@ class KittiDataset(DatasetTemplate):
             return len(self.kitti_infos) * self.total_epochs
         return len(self.kitti_infos)
 
-    def __getitem__(self, index):
-        if self._merge_all_iters_to_one_epoch:
-            index = index % len(self.kitti_infos)
+    def raw_frame(self, index, device=False):
+        """Frame `index` of the infos before prepare_data: {frame_id, calib, image_shape}, with annotations gt_names / gt_boxes
+        [n, 7] (DontCare dropped, camera -> LiDAR, SHIFT_COOR added), gt_boxes2d when GET_ITEM_LIST names it and road_plane when
+        the frame has a plane file, and `points` when GET_ITEM_LIST names them.  device: the points are a CUDA tensor without
+        FOV_POINTS_ONLY too (one upload; SHIFT_COOR is added after it in fp32, the bits of the host addition)."""
         info = copy.deepcopy(self.kitti_infos[index])
         sample_idx = info["point_cloud"]["lidar_idx"]
         img_shape = info["image"]["image_shape"]
         calib = self.get_calib(sample_idx)
-        data = {"frame_id": sample_idx, "calib": calib}
+        data = {"frame_id": sample_idx, "calib": calib, "image_shape": img_shape}
         if "annos" in info:
             annos = common_utils.drop_info_with_name(info["annos"], name="DontCare")
             cam = np.concatenate([annos["location"], annos["dimensions"], annos["rotation_y"][..., np.newaxis]], axis=1).astype(np.float32)
@@ -269,14 +272,20 @@ class KittiDataset(DatasetTemplate):
             points = self.get_lidar(sample_idx)
             if self.fov_points_only:
                 points = self.fov_points(points, calib, img_shape)
+            elif device:
+                points = torch.from_numpy(np.ascontiguousarray(points, dtype=np.float32)).cuda()
             if self.shift_coor:
                 shift = np.array(self.shift_coor, dtype=np.float32)
                 points[:, 0:3] += torch.from_numpy(shift).to(points.device) if torch.is_tensor(points) else shift
             data["points"] = points
-        data = self.prepare_data(data)
+        return data
+
+    def __getitem__(self, index):
+        if self._merge_all_iters_to_one_epoch:
+            index = index % len(self.kitti_infos)
+        data = self.prepare_data(self.raw_frame(index))
         if self.training and data.get("gt_boxes") is not None and len(data["gt_boxes"]) == 0:      # reference dataset.py:152-154
             return self[np.random.randint(len(self))]
-        data["image_shape"] = img_shape
         return data
 
 

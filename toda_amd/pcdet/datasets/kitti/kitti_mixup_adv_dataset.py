@@ -36,6 +36,21 @@ from ..mixup_dataset import MixUpAdvPairPolicy, _boxes7
 from .kitti_dataset import KittiDataset
 
 
+def read_labelled_split(listing, infos):
+    """The indices of a labelled split file, lines of `<frame id> <index into the infos>`, in the file's order; raises when a
+    listed id does not sit at its index (tools/make_labelled_subset.py writes such files)."""
+    listed = []
+    for line in open(listing).read().splitlines():
+        if not line.strip():
+            continue
+        frame, index = line.split()[0], int(line.split()[1])
+        if not 0 <= index < len(infos) or str(infos[index]["point_cloud"]["lidar_idx"]) != frame:
+            have = infos[index]["point_cloud"]["lidar_idx"] if 0 <= index < len(infos) else "no such info"
+            raise ValueError(f"{listing}: line `{line.strip()}` names frame {frame} at index {index}, the infos hold {have} there")
+        listed.append(index)
+    return listed
+
+
 class KittiMixUpAdvDataset(MixUpAdvPairPolicy, KittiDataset):
     def __init__(self, dataset_cfg, class_names, training=True, root_path=None, logger=None, pseudo_info_path=None):
         self.pseudo_info_path = pseudo_info_path if pseudo_info_path is not None else dataset_cfg.get("PSEUDO_INFO_PATH", None)
@@ -62,15 +77,7 @@ class KittiMixUpAdvDataset(MixUpAdvPairPolicy, KittiDataset):
         listing = self.root_path / rel
         if not listing.exists():
             raise FileNotFoundError(f"labelled split file {listing} does not exist: lines of `<frame id> <index into the infos>`")
-        listed = []
-        for line in open(listing).read().splitlines():
-            if not line.strip():
-                continue
-            frame, index = line.split()[0], int(line.split()[1])
-            if not 0 <= index < len(infos) or str(infos[index]["point_cloud"]["lidar_idx"]) != frame:
-                have = infos[index]["point_cloud"]["lidar_idx"] if 0 <= index < len(infos) else "no such info"
-                raise ValueError(f"{listing}: line `{line.strip()}` names frame {frame} at index {index}, the infos hold {have} there")
-            listed.append(index)
+        listed = read_labelled_split(listing, infos)
         path = Path(self.pseudo_info_path)
         if not path.exists():
             raise FileNotFoundError(f"pseudo-label infos {path} do not exist: write them with tools/generate_pseudo_labels --perturb")

@@ -15,12 +15,16 @@ Config keys (as in the reference YAMLs, e.g. tools/cfgs/stage1_targetmix/*.yaml)
   SYNTHETIC: {SOURCE_KIND, TARGET_KIND, NUM_SOURCE, NUM_TARGET, SEED}   (SyntheticMixDataset: no real dataset on the box)
   WaymoDataset: {...}, NuScenesDataset: {...}                             (WaymoNusMixDataset: the two domains' own dataset
   configs, each with CLASS_NAMES and DATA_AUGMENTOR, as the reference's stage-1 YAMLs write them)
+  NuScenesDataset: {...}, KittiDataset: {...}                             (NusKittiMixDataset, likewise)
 
-WaymoNusMixDataset is the dataset those YAMLs name (WaymoNusPolarMixDataset / ...CutMix... / ...LaserMix...: one class here,
-MIX_TYPE decides): source frames from a WaymoDataset, target frames from a NuScenesDataset, both read from disk.  Not built:
-DATA_CONFIG_TEST (evaluate through tools.test on a plain NuScenesDataset yaml).  Of the stage-2 real mixup datasets,
-NuScenesMixUpAdvDataset (nuscenes/nuscenes_mixup_adv_dataset.py) and KittiMixUpAdvDataset (kitti/kitti_mixup_adv_dataset.py) are
-built; the non-adversarial NuScenesMixUpDataset is not.
+TwoDomainMixDataset holds what the real two-domain datasets share: the length, the index policy, both redraws and the
+preparation of one domain's frame.  WaymoNusMixDataset (WaymoNusPolarMixDataset / ...CutMix... / ...LaserMix...) takes source
+frames from a WaymoDataset and target frames from a NuScenesDataset; NusKittiMixDataset (NusKittiPolarMixDataset /
+...CutMix...) takes source frames from a NuScenesDataset and target frames from a KittiDataset.  Each is one class under the
+reference's several names: MIX_TYPE decides the mix.  The trained model is evaluated through the DATA_CONFIG_TEST block of the
+same YAML (tools/test.py), the labelled-subset files the YAMLs name come from tools/make_labelled_subset.py.  Of the stage-2
+real mixup datasets, NuScenesMixUpAdvDataset (nuscenes/nuscenes_mixup_adv_dataset.py) and KittiMixUpAdvDataset
+(kitti/kitti_mixup_adv_dataset.py) are built; the non-adversarial NuScenesMixUpDataset is not.
 """
 import numpy as np
 import torch
@@ -143,19 +147,13 @@ class SyntheticMixDataset(MixDatasetTemplate):
         return data
 
 
-class WaymoNusMixDataset(MixDatasetTemplate):
-    """The real two-domain dataset of stage 1: source frames from a WaymoDataset, target frames from a NuScenesDataset, each
-    built from its sub-block of DATA_CONFIG (own DATA_PATH, CLASS_NAMES and DATA_AUGMENTOR); the joint POINT_FEATURE_ENCODING
-    and DATA_PROCESSOR apply to both domains (reference mix_dataset/waymo_nus_*_dataset.py + two_dataset.py:100-296)."""
+class TwoDomainMixDataset(MixDatasetTemplate):
+    """The real two-domain dataset of stage 1: `self.source` and `self.target` are two datasets read from disk, each built from
+    its sub-block of DATA_CONFIG (own DATA_PATH, CLASS_NAMES and DATA_AUGMENTOR); the joint POINT_FEATURE_ENCODING and
+    DATA_PROCESSOR apply to both domains.  A subclass builds the two datasets and gives the two hooks source_frame(i) and
+    target_frame(i), each a domain's raw frame through _prepare_domain; the length, the index policy and both redraws are here
+    (reference mix_dataset/*_dataset.py + two_dataset.py:100-296)."""
     on_device = True
-
-    def __init__(self, dataset_cfg, class_names, training=True, root_path=None, logger=None):
-        from .nuscenes.nuscenes_dataset import NuScenesDataset
-        from .waymo.waymo_dataset import WaymoDataset
-        super().__init__(dataset_cfg=dataset_cfg, class_names=class_names, training=training, root_path=None, logger=logger)
-        src_cfg, tgt_cfg = dataset_cfg["WaymoDataset"], dataset_cfg["NuScenesDataset"]
-        self.source = WaymoDataset(src_cfg, src_cfg.CLASS_NAMES, training=training, logger=logger)
-        self.target = NuScenesDataset(tgt_cfg, tgt_cfg.CLASS_NAMES, training=training, logger=logger)
 
     @property
     def num_source(self):
@@ -170,26 +168,15 @@ class WaymoNusMixDataset(MixDatasetTemplate):
             return (self.num_source + self.num_target) * self.total_epochs
         return self.num_source + self.num_target
 
-    # ---- one domain's frame as the mix takes it: augmented by the domain's own augmentor, boxes [n, 7] + the class id of the
-    # domain's own list, the domain's first class under the joint first name, features encoded by the joint encoder
     def source_frame(self, index):
-        data = self.source.raw_frame(index)
-        data.pop("num_points_in_gt", None)
-        if "gt_boxes" in data:
-            data["gt_boxes"] = data["gt_boxes"][:, 0:7]
-        return self._prepare_domain(self.source, data)
+        raise NotImplementedError
 
     def target_frame(self, index):
-        data = self.target.raw_frame(index)
-        cfg = self.target.dataset_cfg
-        if "gt_boxes" in data:
-            if cfg.get("SHIFT_COOR", None):
-                data["shift_coor"] = cfg.SHIFT_COOR
-            if cfg.get("SET_NAN_VELOCITY_TO_ZEROS", False):
-                data["gt_boxes"][np.isnan(data["gt_boxes"])] = 0
-            data["gt_boxes"] = data["gt_boxes"][:, 0:7]             # the joint head has no velocity target
-        return self._prepare_domain(self.target, data)
+        raise NotImplementedError
 
+    # ---- one domain's frame as the mix takes it: augmented by the domain's own augmentor, boxes [n, 7] + the class id of the
+    # domain's own list, the domain's first class under the joint first name, features encoded by the joint encoder.  A frame
+    # without an object of the domain's classes leaves with [0, 8] boxes and an empty string array of names.
     def _prepare_domain(self, domain, data):
         names_of = domain.class_names
         if self.training:
@@ -226,3 +213,72 @@ class WaymoNusMixDataset(MixDatasetTemplate):
             return self[np.random.randint(len(self))]
         data.pop("gt_names", None)
         return data
+
+
+def _nuscenes_mix_frame(domain, index):
+    """A NuScenesDataset's raw frame as a mix takes it: shift_coor noted, NaN velocities zeroed, boxes cut to 7 columns (the
+    joint head has no velocity target)."""
+    data = domain.raw_frame(index)
+    cfg = domain.dataset_cfg
+    if "gt_boxes" in data:
+        if cfg.get("SHIFT_COOR", None):
+            data["shift_coor"] = cfg.SHIFT_COOR
+        if cfg.get("SET_NAN_VELOCITY_TO_ZEROS", False):
+            data["gt_boxes"][np.isnan(data["gt_boxes"])] = 0
+        data["gt_boxes"] = data["gt_boxes"][:, 0:7]
+    return data
+
+
+class WaymoNusMixDataset(TwoDomainMixDataset):
+    """Waymo -> nuScenes: source frames from a WaymoDataset, target frames from a NuScenesDataset (reference
+    mix_dataset/waymo_nus_*_dataset.py)."""
+
+    def __init__(self, dataset_cfg, class_names, training=True, root_path=None, logger=None):
+        from .nuscenes.nuscenes_dataset import NuScenesDataset
+        from .waymo.waymo_dataset import WaymoDataset
+        super().__init__(dataset_cfg=dataset_cfg, class_names=class_names, training=training, root_path=None, logger=logger)
+        src_cfg, tgt_cfg = dataset_cfg["WaymoDataset"], dataset_cfg["NuScenesDataset"]
+        self.source = WaymoDataset(src_cfg, src_cfg.CLASS_NAMES, training=training, logger=logger)
+        self.target = NuScenesDataset(tgt_cfg, tgt_cfg.CLASS_NAMES, training=training, logger=logger)
+
+    def source_frame(self, index):
+        data = self.source.raw_frame(index)
+        data.pop("num_points_in_gt", None)
+        if "gt_boxes" in data:
+            data["gt_boxes"] = data["gt_boxes"][:, 0:7]
+        return self._prepare_domain(self.source, data)
+
+    def target_frame(self, index):
+        return self._prepare_domain(self.target, _nuscenes_mix_frame(self.target, index))
+
+
+class NusKittiMixDataset(TwoDomainMixDataset):
+    """nuScenes -> KITTI: source frames from a NuScenesDataset, target frames from a KittiDataset whose points reach the device
+    in raw_frame (reference mix_dataset/nus_kitti_{polarmix,cutmix}_dataset.py:135-334).  A KITTI row has 4 columns where the
+    joint src_feature_list names 5: the encoder only looks up `intensity`, column 3 in both.  Many KITTI frames hold no object
+    of the target classes; such a frame still mixes (source boxes only) and, alone, is redrawn in training.
+
+    Deviations from the reference:
+      * KittiDataset.FOV_POINTS_ONLY: True is honoured in both branches, with the device crop; the reference raises NameError
+        there (`points` is undefined, nus_kitti_polarmix_dataset.py:216-219), which is why its YAML sets False.
+      * GET_ITEM_LIST is read from the KittiDataset sub-block in both branches; the reference reads the top level in the mixed
+        branch and the sub-block in the other.
+      * The merged-epochs index is a modulo, as in WaymoNusMixDataset; the reference multiplies."""
+
+    def __init__(self, dataset_cfg, class_names, training=True, root_path=None, logger=None):
+        from .kitti.kitti_dataset import KittiDataset
+        from .nuscenes.nuscenes_dataset import NuScenesDataset
+        super().__init__(dataset_cfg=dataset_cfg, class_names=class_names, training=training, root_path=None, logger=logger)
+        src_cfg, tgt_cfg = dataset_cfg["NuScenesDataset"], dataset_cfg["KittiDataset"]
+        self.source = NuScenesDataset(src_cfg, src_cfg.CLASS_NAMES, training=training, logger=logger)
+        self.target = KittiDataset(tgt_cfg, tgt_cfg.CLASS_NAMES, training=training, logger=logger)
+
+    @property
+    def num_target(self):
+        return len(self.target.kitti_infos)
+
+    def source_frame(self, index):
+        return self._prepare_domain(self.source, _nuscenes_mix_frame(self.source, index))
+
+    def target_frame(self, index):
+        return self._prepare_domain(self.target, self.target.raw_frame(index, device=True))       # the boxes have 7 columns

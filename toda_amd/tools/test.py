@@ -2,7 +2,8 @@
 """tools/test.py of the reference (:21-204), single-checkpoint path:
     python -m toda_amd.tools.test --cfg_file toda_amd/tools/cfgs/models/centerpoint_voxel_waymo.yaml --ckpt out/ckpt/checkpoint_epoch_1.pth
 Flags: --cfg_file --batch_size --workers --extra_tag --ckpt --launcher {none,pytorch} --eval_tag --save_to_file --set ...
-(--eval_all / --ckpt_dir polling of a training run is not built)."""
+(--eval_all / --ckpt_dir polling of a training run is not built).  A configuration with a DATA_CONFIG_TEST block is evaluated on
+that block's dataset under that block's CLASS_NAMES (test_data_config)."""
 import argparse
 import datetime
 import re
@@ -41,6 +42,19 @@ def parse_config(argv=None):
     return args, cfg
 
 
+def test_data_config(config):
+    """(dataset config, class names) of the test loader: the DATA_CONFIG_TEST block with its own CLASS_NAMES where the
+    configuration has one (reference tools/test.py:185-199; a stage-1 model is trained on a mix dataset under the joint name
+    `car` and evaluated on the target dataset alone, under that dataset's own name), else DATA_CONFIG and CLASS_NAMES."""
+    block = config.get("DATA_CONFIG_TEST", None)
+    if block is not None:
+        return block, list(block.CLASS_NAMES)
+    return config.DATA_CONFIG, list(config.CLASS_NAMES)
+
+
+test_data_config.__test__ = False       # a helper of this tool, not a test case
+
+
 def eval_single_ckpt(model, test_loader, args, eval_output_dir, logger, epoch_id, dist_test=False):
     if args.ckpt is not None:
         model.load_params_from_file(filename=args.ckpt, logger=logger, to_cpu=dist_test)
@@ -65,15 +79,16 @@ def main(argv=None):
     output_dir = root / cfg_.EXP_GROUP_PATH / cfg_.TAG / args.extra_tag
     num = re.findall(r"\d+", Path(args.ckpt).stem) if args.ckpt else []
     epoch_id = num[-1] if num else "no_number"
-    eval_output_dir = output_dir / "eval" / f"epoch_{epoch_id}" / cfg_.DATA_CONFIG.get("DATA_SPLIT", {}).get("test", "val") / args.eval_tag
+    data_cfg, class_names = test_data_config(cfg_)
+    eval_output_dir = output_dir / "eval" / f"epoch_{epoch_id}" / data_cfg.get("DATA_SPLIT", {}).get("test", "val") / args.eval_tag
     eval_output_dir.mkdir(parents=True, exist_ok=True)
     logger = common_utils.create_logger(eval_output_dir / ("log_eval_%s.txt" % datetime.datetime.now().strftime("%Y%m%d-%H%M%S")),
                                         rank=cfg_.LOCAL_RANK)
     logger.info("**********************Start logging**********************")
     log_config_to_file(cfg_, logger=logger)
-    test_set, test_loader, _ = build_dataloader(dataset_cfg=cfg_.DATA_CONFIG, class_names=cfg_.CLASS_NAMES, batch_size=args.batch_size,
+    test_set, test_loader, _ = build_dataloader(dataset_cfg=data_cfg, class_names=class_names, batch_size=args.batch_size,
                                                 dist=dist_test, workers=args.workers, logger=logger, training=False)
-    model = build_network(model_cfg=cfg_.MODEL, num_class=len(cfg_.CLASS_NAMES), dataset=test_set)
+    model = build_network(model_cfg=cfg_.MODEL, num_class=len(class_names), dataset=test_set)
     with torch.no_grad():
         return eval_single_ckpt(model, test_loader, args, eval_output_dir, logger, epoch_id, dist_test=dist_test)
 
