@@ -665,6 +665,15 @@ int toda_sweeps_merge(const float* rows, int n, int n_sweeps, const int32_t* off
                       const int32_t* has_matrix_host, const int32_t* drop_ego_host, const double* time_lags_host,
                       float radius, const float* shift_host, float* out, int32_t* flags, void* stream);
 
+/* toda_sweeps_merge with an ego cut of two half-sides (the Lyft sample, pcdet/datasets/lyft/lyft_dataset.py remove_ego_points:
+ * 1.5 m x 1.0 m): the same kernel and the same arguments, except that
+ *   flags[j] = !(drop_ego[s] && |x| < radius_x && |y| < radius_y)   raw fp32 coordinates, strict, a NaN keeps the row
+ * toda_sweeps_merge(radius) is toda_sweeps_merge_rect(radius, radius), bit for bit.  The same argument errors, a half-side that
+ * is negative or NaN among them, return -1; n == 0 succeeds without a launch. */
+int toda_sweeps_merge_rect(const float* rows, int n, int n_sweeps, const int32_t* offsets_host, const double* matrices_host,
+                           const int32_t* has_matrix_host, const int32_t* drop_ego_host, const double* time_lags_host,
+                           float radius_x, float radius_y, const float* shift_host, float* out, int32_t* flags, void* stream);
+
 /* Point pass of a processed Waymo frame (csrc/waymo_frame.hip; pcdet/datasets/waymo/waymo_dataset.py get_lidar):
  *   rows [n, c_in] fp32, device, c_in >= 6: x, y, z, intensity, elongation, NLZ flag (further columns are not read)
  *   out[j]   = (x, y, z, (float)tanh((double)intensity), elongation)  [n, 5] fp32, written for every row, kept or not; the fp64
@@ -976,6 +985,43 @@ int toda_waymo_eval_match(const double* iou, const float* pred_score, const doub
                           const int32_t* gt_off_host, const long long* iou_off_host, const int32_t* seg_type_host, int n_seg,
                           long long n_pairs, const float* cutoffs_host, long long* tp, long long* fn, long long* fp,
                           double* sum_ha, int32_t* match_dbg, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The device parts of the Lyft detection metric (mAP over ascending IoU cut-offs; reference
+ * pcdet/datasets/lyft/lyft_mAP_eval/lyft_eval.py get_average_precisions).  fp64 and integers throughout, no atomics: two runs
+ * give the same bits.  A segment is one (sample, class); both sides are stored segment after segment as rows of 8 doubles in
+ * the global frame: centre x y z, c, s, width, length, height, where (c, s) is the first column of the box's rotation and is
+ * NOT normalised.  The ground rectangle is centre +- length / 2 (c, s) +- width / 2 (s, -c), the volume width * length * height.
+ * pred_off_host / gt_off_host (HOST, int32 [n_seg + 1]) are the CSR offsets of both sides; they are checked on the host (null,
+ * negative, descending, not running from 0 to the total: refused before anything is launched) and copied into ws.  A segment
+ * has no size cap: the kernels walk a long side in chunks.
+ *
+ * toda_lyft_eval_best: for every prediction the largest IoU over the ground truths of its segment and the position within the
+ * segment of the first ground truth that attains it (numpy's max / argmax); best_gt = -1 and best_iou = -inf in a segment
+ * without ground truths.  IoU: the prediction's rectangle clipped exactly by the four edges of the ground truth's (no corner
+ * margins), shoelace area, times the overlap of the z intervals, divided by volA + volB - inter, clamped to [0, 1].  Sizes must
+ * be positive and every value finite (the caller's check).
+ *
+ * toda_lyft_eval_flags: tp [n_thresholds, n_pred] uint8.  Within a segment q stands before p iff score_q > score_p, or the
+ * scores are equal and q is stored earlier (a stable descending sort).  With m_p the largest best_iou_q over the q before p
+ * that have best_gt_q == best_gt_p (-inf when there is none),
+ *   tp[t, p] = best_iou_p > thresholds[t] && !(m_p > thresholds[t])
+ * which is the reference's sequential walk: a ground truth is claimed at t by the first prediction in that order whose largest
+ * IoU exceeds t and falls on it.  A prediction is a false positive wherever it is not a true positive.  thresholds_host (HOST,
+ * fp64) holds 1 .. TODA_LYFT_MAX_CUTOFFS strictly ascending values; score fp64 [n_pred] must hold no NaN (the caller's check).
+ * toda_lyft_eval_flags_chunk(): the number of predictions of one LDS stage of that kernel.
+ *
+ * n_pred == 0 or n_seg == 0 succeeds without a launch.  ws: toda_lyft_eval_workspace_bytes(n_seg) bytes, for either call.
+ * ---------------------------------------------------------------------- */
+#define TODA_LYFT_MAX_CUTOFFS 16
+int toda_lyft_eval_flags_chunk(void);
+size_t toda_lyft_eval_workspace_bytes(int n_seg);
+int toda_lyft_eval_best(const double* pred, int n_pred, const double* gt, int n_gt, const int32_t* pred_off_host,
+                        const int32_t* gt_off_host, int n_seg, double* best_iou, int32_t* best_gt, void* ws, size_t ws_bytes,
+                        void* stream);
+int toda_lyft_eval_flags(const double* score, const double* best_iou, const int32_t* best_gt, int n_pred,
+                         const int32_t* pred_off_host, int n_seg, const double* thresholds_host, int n_thresholds, uint8_t* tp,
+                         void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The consistency term of the stage-2 step (reference pcdet/models/__init__.py get_consistency_loss): mutual

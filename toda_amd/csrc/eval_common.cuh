@@ -1,6 +1,6 @@
-// What kitti_eval.hip, nuscenes_eval.hip and waymo_eval.hip share: the lexicographic pick and the sum over a wave, the counting rank
+// What kitti_eval.hip, nuscenes_eval.hip, waymo_eval.hip and lyft_eval.hip share: the lexicographic pick and the sum over a wave, the counting rank
 // by score into LDS, a segment's span with its guard, the run-then-tree fold, and on the host the CSR check, the workspace carver
-// and the copy of a host table into its slot.  The three intersections (ev_rect_inter, we_iou, the centre distance) are NOT here:
+// and the copy of a host table into its slot.  The intersections (ev_rect_inter, we_iou, ly_iou, the centre distance) are NOT here:
 // each is pinned to its own metric's definition.  Everything is inline or static: every translation unit that
 // includes this header compiles its own copy.
 #pragma once

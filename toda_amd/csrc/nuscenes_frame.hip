@@ -12,6 +12,9 @@
 //   x' = (float)(((double)x * m00 + (double)y * m01 + (double)z * m02) + m03)      numpy's float64 dot assigned into fp32
 //   x' += shift[0]                                                                  in fp32, after the rounding (SHIFT_COOR)
 // The ego test reads the raw fp32 coordinates; a NaN compares false, so the row is kept, as in numpy.
+//
+// The ego cut is a rectangle of two half-sides: toda_sweeps_merge passes its radius for both (nuScenes' square),
+// toda_sweeps_merge_rect passes them apart (Lyft's 1.5 m x 1.0 m, lyft_dataset.py remove_ego_points).  One kernel for both.
 #include <string.h>
 
 #include "common.h"
@@ -28,7 +31,7 @@ struct SweepTable {
     int32_t offset[SWEEPS_MAX + 1];
     float lag[SWEEPS_MAX];
     uint32_t has_matrix, drop_ego;     // bit s = sweep s
-    float radius;
+    float radius_x, radius_y;          // half-sides of the ego rectangle
     int32_t has_shift;
     float shift[3];
 };
@@ -43,7 +46,7 @@ sweeps_merge_kernel(const float* __restrict__ rows, SweepTable t, float* __restr
     const float* p = rows + j * SWEEP_IN_COLS;
     float x = p[0], y = p[1], z = p[2];
     const float intensity = p[3];
-    const bool ego = ((t.drop_ego >> s) & 1u) && fabsf(x) < t.radius && fabsf(y) < t.radius;
+    const bool ego = ((t.drop_ego >> s) & 1u) && fabsf(x) < t.radius_x && fabsf(y) < t.radius_y;
     if ((t.has_matrix >> s) & 1u) {
         const double* m = t.m[s];
         const double dx = x, dy = y, dz = z;
@@ -63,21 +66,20 @@ using namespace toda;
 
 extern "C" int toda_sweeps_merge_max_sweeps(void) { return SWEEPS_MAX; }
 
-extern "C" int toda_sweeps_merge(const float* rows, int n, int n_sweeps, const int32_t* offsets_host, const double* matrices_host,
-                                 const int32_t* has_matrix_host, const int32_t* drop_ego_host, const double* time_lags_host,
-                                 float radius, const float* shift_host, float* out, int32_t* flags, void* stream) {
-    TODA_CHECK_ARG(n >= 0, "sweeps_merge: need n >= 0");
-    TODA_CHECK_ARG(n_sweeps >= 1 && n_sweeps <= SWEEPS_MAX, "sweeps_merge: %d sweeps, supported are 1 to %d (key frame included)", n_sweeps, SWEEPS_MAX);
-    TODA_CHECK_ARG(radius >= 0.f, "sweeps_merge: the ego radius must be a number >= 0");
-    PT_CHECK_TABLES(offsets_host && matrices_host && has_matrix_host && drop_ego_host && time_lags_host, "sweeps_merge: null sweep table");
-    TODA_CHECK_ARG(rows && out && flags, "sweeps_merge: null rows, out or flags");
-    TODA_CHECK_ARG(offsets_host[0] == 0 && offsets_host[n_sweeps] == n, "sweeps_merge: row offsets must run from 0 to n = %d", n);
+// the host side of both entry points; `who` names the caller in the messages
+static int sweeps_merge_launch(const char* who, const float* rows, int n, int n_sweeps, const int32_t* offsets_host,
+                               const double* matrices_host, const int32_t* has_matrix_host, const int32_t* drop_ego_host,
+                               const double* time_lags_host, float radius_x, float radius_y, const float* shift_host, float* out,
+                               int32_t* flags, void* stream) {
+    PT_CHECK_TABLES(offsets_host && matrices_host && has_matrix_host && drop_ego_host && time_lags_host, "%s: null sweep table", who);
+    TODA_CHECK_ARG(rows && out && flags, "%s: null rows, out or flags", who);
+    TODA_CHECK_ARG(offsets_host[0] == 0 && offsets_host[n_sweeps] == n, "%s: row offsets must run from 0 to n = %d", who, n);
     SweepTable t;
     memset(&t, 0, sizeof(t));
     int longest = 0;
     for (int s = 0; s < n_sweeps; ++s) {
         const int count = offsets_host[s + 1] - offsets_host[s];
-        TODA_CHECK_ARG(count >= 0, "sweeps_merge: row offsets decrease at sweep %d", s);
+        TODA_CHECK_ARG(count >= 0, "%s: row offsets decrease at sweep %d", who, s);
         longest = count > longest ? count : longest;
         t.offset[s] = offsets_host[s];
         t.lag[s] = (float)time_lags_host[s];
@@ -88,7 +90,8 @@ extern "C" int toda_sweeps_merge(const float* rows, int n, int n_sweeps, const i
         if (drop_ego_host[s]) t.drop_ego |= 1u << s;
     }
     t.offset[n_sweeps] = n;
-    t.radius = radius;
+    t.radius_x = radius_x;
+    t.radius_y = radius_y;
     if (shift_host) {
         t.has_shift = 1;
         for (int i = 0; i < 3; ++i) t.shift[i] = shift_host[i];
@@ -96,4 +99,25 @@ extern "C" int toda_sweeps_merge(const float* rows, int n, int n_sweeps, const i
     hipLaunchKernelGGL(sweeps_merge_kernel, dim3(cdiv(longest, PT_BLOCK), n_sweeps), dim3(PT_BLOCK), 0, (hipStream_t)stream, rows, t, out, flags);
     TODA_LAUNCH_CHECK();
     return TODA_OK;
+}
+
+extern "C" int toda_sweeps_merge(const float* rows, int n, int n_sweeps, const int32_t* offsets_host, const double* matrices_host,
+                                 const int32_t* has_matrix_host, const int32_t* drop_ego_host, const double* time_lags_host,
+                                 float radius, const float* shift_host, float* out, int32_t* flags, void* stream) {
+    TODA_CHECK_ARG(n >= 0, "sweeps_merge: need n >= 0");
+    TODA_CHECK_ARG(n_sweeps >= 1 && n_sweeps <= SWEEPS_MAX, "sweeps_merge: %d sweeps, supported are 1 to %d (key frame included)", n_sweeps, SWEEPS_MAX);
+    TODA_CHECK_ARG(radius >= 0.f, "sweeps_merge: the ego radius must be a number >= 0");
+    return sweeps_merge_launch("sweeps_merge", rows, n, n_sweeps, offsets_host, matrices_host, has_matrix_host, drop_ego_host, time_lags_host,
+                               radius, radius, shift_host, out, flags, stream);
+}
+
+extern "C" int toda_sweeps_merge_rect(const float* rows, int n, int n_sweeps, const int32_t* offsets_host, const double* matrices_host,
+                                      const int32_t* has_matrix_host, const int32_t* drop_ego_host, const double* time_lags_host,
+                                      float radius_x, float radius_y, const float* shift_host, float* out, int32_t* flags, void* stream) {
+    TODA_CHECK_ARG(n >= 0, "sweeps_merge_rect: need n >= 0");
+    TODA_CHECK_ARG(n_sweeps >= 1 && n_sweeps <= SWEEPS_MAX, "sweeps_merge_rect: %d sweeps, supported are 1 to %d (key frame included)", n_sweeps,
+                   SWEEPS_MAX);
+    TODA_CHECK_ARG(radius_x >= 0.f && radius_y >= 0.f, "sweeps_merge_rect: the ego half-sides must be numbers >= 0");
+    return sweeps_merge_launch("sweeps_merge_rect", rows, n, n_sweeps, offsets_host, matrices_host, has_matrix_host, drop_ego_host,
+                               time_lags_host, radius_x, radius_y, shift_host, out, flags, stream);
 }

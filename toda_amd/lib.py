@@ -139,6 +139,7 @@ SIGNATURES = {
     "toda_points_fov_flags": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
     "toda_sweeps_merge_max_sweeps": (_i, []),
     "toda_sweeps_merge": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp]),
+    "toda_sweeps_merge_rect": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _vp, _vp]),
     "toda_waymo_frame": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "toda_adv_edit_max_boxes": (_i, []),
     "toda_adv_edit_chunk": (_i, []),
@@ -175,6 +176,10 @@ SIGNATURES = {
     "toda_waymo_eval_match_workspace_bytes": (_sz, [_i]),
     "toda_waymo_eval_iou": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, C.c_longlong, _vp, _vp, _sz, _vp]),
     "toda_waymo_eval_match": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, C.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "toda_lyft_eval_flags_chunk": (_i, []),
+    "toda_lyft_eval_workspace_bytes": (_sz, [_i]),
+    "toda_lyft_eval_best": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "toda_lyft_eval_flags": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _sz, _vp]),
     "toda_consistency_workspace_bytes": (_sz, [_i, _i, _i]),
     "toda_consistency_loss": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, C.c_float, _vp, _vp, _sz, _vp]),
 }

@@ -2038,6 +2038,48 @@ def waymo_eval_match(iou, score, pred_heading, gt_heading, gt_level, pred_off, g
     return tp, fn, fp, sum_ha, match
 
 
+LYFT_MAX_CUTOFFS = 16                                            # TODA_LYFT_MAX_CUTOFFS of include/toda.h
+LYFT_IOU_THRESHOLDS = (0.5, 0.55, 0.6, 0.65, 0.7, 0.75, 0.8, 0.85, 0.9, 0.95)
+
+
+def lyft_eval_best(pred, gt, pred_off, gt_off):
+    """The Lyft metric's largest IoU per prediction (toda_lyft_eval_best) -> (best_iou fp64 [n_pred], best_gt int32 [n_pred]: the
+    position within the segment of the first ground truth that attains it; -inf and -1 in a segment without ground truths).
+    pred / gt fp64 [., 8] = centre x y z, c, s, width, length, height in the global frame, in segment order; pred_off / gt_off
+    are HOST int32 CSR offsets [n_seg + 1]."""
+    pred, gt = (_eval_arg(t, torch.float64, "lyft_eval_best: boxes") for t in (pred, gt))
+    if pred.dim() != 2 or pred.shape[1] != 8 or gt.dim() != 2 or gt.shape[1] != 8:
+        raise RuntimeError("lyft_eval_best: pred and gt must be [., 8]")
+    pred_off, gt_off = (_eval_host(a, np.int32) for a in (pred_off, gt_off))
+    if pred_off.ndim != 1 or pred_off.shape != gt_off.shape or pred_off.shape[0] < 1:
+        raise RuntimeError("lyft_eval_best: pred_off and gt_off must be [n_seg + 1]")
+    n_seg, n_pred, n_gt = int(pred_off.shape[0]) - 1, int(pred.shape[0]), int(gt.shape[0])
+    best_iou = torch.empty((n_pred,), dtype=torch.float64, device=pred.device)
+    best_gt = torch.empty((n_pred,), dtype=torch.int32, device=pred.device)
+    _eval_call("toda_lyft_eval_best", ("toda_lyft_eval_workspace_bytes", n_seg), pred.device, L.ptr(pred), n_pred, L.ptr(gt), n_gt,
+               pred_off.ctypes.data, gt_off.ctypes.data, n_seg, L.ptr(best_iou), L.ptr(best_gt), host_arrays=True)
+    return best_iou, best_gt
+
+
+def lyft_eval_flags(score, best_iou, best_gt, pred_off, thresholds=LYFT_IOU_THRESHOLDS):
+    """The Lyft metric's true-positive flags (toda_lyft_eval_flags) -> tp uint8 [T, n_pred]: prediction p is a TP at cut-off t iff
+    its largest IoU exceeds t and no prediction before it in its segment's (score descending, position) order has the same
+    argmax and exceeds t.  score / best_iou fp64 [n_pred] and best_gt int32 [n_pred] in segment order; pred_off HOST int32
+    [n_seg + 1]; thresholds: 1 to LYFT_MAX_CUTOFFS ascending HOST values."""
+    score, best_iou = (_eval_arg(t, torch.float64, "lyft_eval_flags: scores and best IoU") for t in (score, best_iou))
+    best_gt = _eval_arg(best_gt, torch.int32, "lyft_eval_flags: best_gt")
+    pred_off, ths = _eval_host(pred_off, np.int32), _eval_host(thresholds, np.float64)
+    if pred_off.ndim != 1 or pred_off.shape[0] < 1 or ths.ndim != 1:
+        raise RuntimeError("lyft_eval_flags: pred_off must be [n_seg + 1] and the cut-offs a vector")
+    n_seg, n_pred = int(pred_off.shape[0]) - 1, int(score.numel())
+    if best_iou.numel() != n_pred or best_gt.numel() != n_pred:
+        raise RuntimeError("lyft_eval_flags: one score, one best IoU and one best ground truth per prediction")
+    tp = torch.empty((int(ths.shape[0]), n_pred), dtype=torch.uint8, device=score.device)
+    _eval_call("toda_lyft_eval_flags", ("toda_lyft_eval_workspace_bytes", n_seg), score.device, L.ptr(score), L.ptr(best_iou), L.ptr(best_gt),
+               n_pred, pred_off.ctypes.data, n_seg, ths.ctypes.data, int(ths.shape[0]), L.ptr(tp), host_arrays=True)
+    return tp
+
+
 class _CenterLoss(torch.autograd.Function):
     """CenterHead.get_loss of one head group in three launches forward / one backward (toda_center_loss_*).
     apply(n, hm_logits, reg_0..reg_{n-1}, heatmap, inds, mask, target_boxes, code_weights, cls_weight, loc_weight)
@@ -2523,18 +2565,14 @@ def points_fov_flags(points, m, p2, image_shape, n_dev=None):
     return _row_pass("toda_points_fov_flags", points, n_dev, 0, L.hptr(mh), L.hptr(ph), int(image_shape[0]), int(image_shape[1]))
 
 
-def sweeps_merge(rows, offsets, matrices, time_lags, drop_ego, radius=1.0, shift=None):
-    """The multi-sweep merge of a nuScenes sample (C ABI: toda_sweeps_merge).  `rows`: [n, 5] fp32 device rows (x, y, z,
-    intensity, ring) of the sample's S files one after the other, sweep s at rows offsets[s] .. offsets[s + 1] - 1.  Host side,
-    per sweep: `matrices[s]` a float64 matrix of 3 or 4 rows x 4 columns into the key frame, or None (rows pass through);
-    `time_lags[s]`; `drop_ego[s]`: flag the rows with |x| < radius and |y| < radius.  `shift`: 3 fp32 values added after the
-    fp32 rounding.  Returns (out [n, 5] fp32: x' y' z' intensity time, flags [n] int32: 1 = keep) for ops.RowBuffer."""
+def _sweeps_merge(name, radii, rows, offsets, matrices, time_lags, drop_ego, shift):
     lib = L.load()
+    who = name[len("toda_"):]
     if rows.dim() != 2 or rows.shape[1] != 5 or rows.dtype != torch.float32:
-        raise RuntimeError("sweeps_merge: rows must be [n, 5] float32")
+        raise RuntimeError(f"{who}: rows must be [n, 5] float32")
     n, s = rows.shape[0], len(matrices)
     if not (len(offsets) == s + 1 and len(time_lags) == s and len(drop_ego) == s):
-        raise RuntimeError("sweeps_merge: offsets, matrices, time_lags and drop_ego disagree on the number of sweeps")
+        raise RuntimeError(f"{who}: offsets, matrices, time_lags and drop_ego disagree on the number of sweeps")
     mats = np.zeros((max(s, 1), 12), np.float64)
     for k, m in enumerate(matrices):
         if m is not None:
@@ -2544,10 +2582,25 @@ def sweeps_merge(rows, offsets, matrices, time_lags, drop_ego, radius=1.0, shift
     off, mh = L.host_i32(offsets), L.host_f64(mats.reshape(-1))
     has, ego, lag = L.host_i32([m is not None for m in matrices]), L.host_i32([bool(d) for d in drop_ego]), L.host_f64(time_lags)
     sh = L.host_f32(np.asarray(shift, np.float32).reshape(3)) if shift is not None else None
-    rc = lib.toda_sweeps_merge(L.ptr(rows), n, s, L.hptr(off), L.hptr(mh), L.hptr(has), L.hptr(ego), L.hptr(lag), float(radius),
-                               L.hptr(sh) if sh is not None else None, L.ptr(out), L.ptr(flags), L.stream())
-    L.check(rc, "toda_sweeps_merge")
+    rc = getattr(lib, name)(L.ptr(rows), n, s, L.hptr(off), L.hptr(mh), L.hptr(has), L.hptr(ego), L.hptr(lag), *[float(r) for r in radii],
+                            L.hptr(sh) if sh is not None else None, L.ptr(out), L.ptr(flags), L.stream())
+    L.check(rc, name)
     return out, flags
+
+
+def sweeps_merge(rows, offsets, matrices, time_lags, drop_ego, radius=1.0, shift=None):
+    """The multi-sweep merge of a nuScenes sample (C ABI: toda_sweeps_merge).  `rows`: [n, 5] fp32 device rows (x, y, z,
+    intensity, ring) of the sample's S files one after the other, sweep s at rows offsets[s] .. offsets[s + 1] - 1.  Host side,
+    per sweep: `matrices[s]` a float64 matrix of 3 or 4 rows x 4 columns into the key frame, or None (rows pass through);
+    `time_lags[s]`; `drop_ego[s]`: flag the rows with |x| < radius and |y| < radius.  `shift`: 3 fp32 values added after the
+    fp32 rounding.  Returns (out [n, 5] fp32: x' y' z' intensity time, flags [n] int32: 1 = keep) for ops.RowBuffer."""
+    return _sweeps_merge("toda_sweeps_merge", (radius,), rows, offsets, matrices, time_lags, drop_ego, shift)
+
+
+def sweeps_merge_rect(rows, offsets, matrices, time_lags, drop_ego, radius_x, radius_y, shift=None):
+    """sweeps_merge with an ego cut of two half-sides (C ABI: toda_sweeps_merge_rect; the Lyft sample): drop_ego[s] flags the
+    rows with |x| < radius_x and |y| < radius_y.  Everything else as sweeps_merge."""
+    return _sweeps_merge("toda_sweeps_merge_rect", (radius_x, radius_y), rows, offsets, matrices, time_lags, drop_ego, shift)
 
 
 def waymo_frame(rows, use_nlz=True):

@@ -1,8 +1,8 @@
 """Dataset registry and dataloader builder (reference pcdet/datasets/__init__.py:25-97).  KittiDataset reads the KITTI
-object benchmark, NuScenesDataset the nuScenes sweeps and WaymoDataset the processed Waymo frames from disk;
-WaymoNusMixDataset (Waymo -> nuScenes) and NusKittiMixDataset (nuScenes -> KITTI) mix two of them for TODA stage 1, each under
-the reference's per-mix names; the readers of the other real datasets (Lyft / ...) are out of scope,
-their shapes come from the synthetic datasets, which expose the same attributes and the same collate contract."""
+object benchmark, NuScenesDataset the nuScenes sweeps, WaymoDataset the processed Waymo frames and LyftDataset the Lyft
+sweeps from disk; WaymoNusMixDataset (Waymo -> nuScenes) and NusKittiMixDataset (nuScenes -> KITTI) mix two of them for TODA
+stage 1, each under the reference's per-mix names; the synthetic datasets expose the same attributes and the same collate
+contract."""
 from functools import partial
 
 import torch
@@ -13,6 +13,7 @@ from ..utils import common_utils
 from .dataset import DatasetTemplate
 from .kitti.kitti_dataset import KittiDataset
 from .kitti.kitti_mixup_adv_dataset import KittiMixUpAdvDataset
+from .lyft.lyft_dataset import LyftDataset
 from .nuscenes.nuscenes_dataset import NuScenesDataset
 from .nuscenes.nuscenes_mixup_adv_dataset import NuScenesMixUpAdvDataset
 from .synthetic import SyntheticLidarDataset, SyntheticPairDataset
@@ -27,6 +28,7 @@ __all__ = {
     "NuScenesDataset": NuScenesDataset,
     "NuScenesMixUpAdvDataset": NuScenesMixUpAdvDataset,
     "WaymoDataset": WaymoDataset,
+    "LyftDataset": LyftDataset,
     "WaymoNusMixDataset": WaymoNusMixDataset,
     "WaymoNusPolarMixDataset": WaymoNusMixDataset,           # the reference's three names: MIX_TYPE decides which mix runs
     "WaymoNusCutMixDataset": WaymoNusMixDataset,
