@@ -42,7 +42,7 @@ extern "C" {
 
 /* Bits of the device fault word: the kernels whose workgroups wait for each other inside one launch bound their spins;
  * a wait that gives up raises its bit and the launch finishes with invalid numbers instead of hanging the GPU. */
-#define TODA_FAULT_BN2D 1u /* bn2d_fwd/bwd_split_kernel: partner never published */
+#define TODA_FAULT_BN2D 1u /* bn2d_fwd/bwd_kernel<V, 0, K, RELU> (one workgroup per plane): partner never published */
 #define TODA_FAULT_WINO 2u /* wino_fwd_ws_kernel: stream-K contributor never published */
 #define TODA_FAULT_FPS 4u  /* fps_multi_kernel: a workgroup of the sample's group never arrived */
 

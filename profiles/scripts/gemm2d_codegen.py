@@ -39,7 +39,7 @@ def key(name):
     raise SystemExit("unparsed kernel name " + name)
 
 
-def resources(path):
+def resources(path, key=key):
     out, cur = {}, None
     for line in open(path):
         m = re.search(r"remark:\s+Function Name: (\S+)", line)

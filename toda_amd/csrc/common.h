@@ -34,6 +34,8 @@ void set_error(const char* fmt, ...);
 // fault_take() returns and clears it.  Kernels raise bits with fault_raise().
 unsigned* fault_word_dev();
 unsigned fault_take();
+// the kernels behind the bits of a fault word, for an error message (valid until this thread's next call)
+const char* fault_names(unsigned word);
 constexpr unsigned FAULT_SPIN_LIMIT = 1u << 21;      // polls of ~1 us: about two seconds
 __device__ __forceinline__ void fault_raise(unsigned* word, unsigned bit) {
     if (word) __hip_atomic_fetch_or(word, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);

@@ -33,7 +33,7 @@ int cu_count() {
 }
 
 // ---- device fault word ------------------------------------------------------------------------------------------------
-// The two kernels whose workgroups wait for each other inside one launch (bn2d_*_split_kernel, wino_fwd_ws_kernel) bound
+// The two kernels whose workgroups wait for each other inside one launch (the per-plane bn2d_*_kernel<V, 0, K, RELU>, wino_fwd_ws_kernel) bound
 // their spins: a wait that outlives FAULT_SPIN_LIMIT polls raises a word in host-mapped pinned memory and falls through
 // (the launch then finishes with wrong numbers instead of hanging the GPU).  The host reads that word without any device
 // synchronisation at the next call of the same family and through toda_device_fault().
@@ -71,6 +71,13 @@ unsigned fault_take() {
     return v;
 }
 
+const char* fault_names(unsigned word) {
+    static thread_local char names[128];
+    snprintf(names, sizeof(names), "%s%s%s", (word & TODA_FAULT_BN2D) ? "bn2d_*_kernel<V, 0, K, RELU> (per plane) " : "", (word & TODA_FAULT_WINO) ? "wino_fwd_ws_kernel " : "",
+             (word & TODA_FAULT_FPS) ? "fps_multi_kernel" : "");
+    return names;
+}
+
 }  // namespace toda
 
 extern "C" const char* toda_last_error(void) { return toda::g_err; }
@@ -79,8 +86,6 @@ extern "C" int toda_abi_version(void) { return 3; }
 extern "C" int toda_device_fault(void) {
     const unsigned v = toda::fault_take();
     if (!v) return TODA_OK;
-    toda::set_error("device fault word 0x%x: a bounded inter-workgroup wait gave up (%s%s%s); the results of that launch are invalid",
-                    v, (v & TODA_FAULT_BN2D) ? "bn2d split kernel " : "", (v & TODA_FAULT_WINO) ? "wino_fwd_ws_kernel " : "",
-                    (v & TODA_FAULT_FPS) ? "fps_multi_kernel" : "");
+    toda::set_error("device fault word 0x%x: a bounded inter-workgroup wait gave up (%s); the results of that launch are invalid", v, toda::fault_names(v));
     return TODA_EFAULT;
 }

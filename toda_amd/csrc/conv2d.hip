@@ -1282,9 +1282,9 @@ extern "C" int toda_conv3x3_fwd(const float* x, const float* u, const float* bia
             // a bounded wait of an earlier launch gave up: its flags may still be up - put the workspace back into its all-zero
             // state behind that launch and report
             (void)hipMemsetAsync(ws, 0, WS_FLAG_BYTES, (hipStream_t)stream);
-            toda::set_error("conv3x3_fwd: device fault word 0x%x raised by an earlier launch (bounded inter-workgroup wait gave up: %s%s) - its "
+            toda::set_error("conv3x3_fwd: device fault word 0x%x raised by an earlier launch (bounded inter-workgroup wait gave up: %s) - its "
                             "results are invalid; the stream-K flags have been re-zeroed (TODA_WINO_VARIANT=0 selects the kernel without hand-offs)",
-                            fv, (fv & TODA_FAULT_BN2D) ? "bn2d split kernel " : "", (fv & TODA_FAULT_WINO) ? "wino_fwd_ws_kernel" : "");
+                            fv, fault_names(fv));
             return TODA_EFAULT;
         }
         hipLaunchKernelGGL(wino_fwd_ws_kernel, dim3(grid), dim3(WS_BLOCK), 0, (hipStream_t)stream, x, u, bias, y, g, n_units, slabs, flags,
