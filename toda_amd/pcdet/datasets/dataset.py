@@ -11,6 +11,47 @@ from .processor.data_processor import DataProcessor
 from .processor.point_feature_encoder import PointFeatureEncoder
 
 
+def lidar_prediction_dicts(batch_dict, pred_dicts, class_names, with_labels=True, shift=None):
+    """The record of the datasets read from disk: per frame {name, score, boxes_lidar, pred_labels (with_labels), frame_id,
+    metadata}.  A frame without detections keeps the zero-length float fields of the reference's template; `shift`
+    (SHIFT_COOR) is taken off the box centres."""
+    annos = []
+    for index, box_dict in enumerate(pred_dicts):
+        scores = box_dict["pred_scores"].detach().cpu().numpy()
+        boxes = box_dict["pred_boxes"].detach().cpu().numpy()
+        labels = box_dict["pred_labels"].detach().cpu().numpy()
+        n = scores.shape[0]
+        anno = {"name": np.zeros(n), "score": np.zeros(n), "boxes_lidar": np.zeros([n, 7])}
+        if with_labels:
+            anno["pred_labels"] = np.zeros(n)
+        if n:
+            if shift:
+                boxes[:, 0:3] -= shift
+            anno.update(name=np.array(class_names)[labels - 1], score=scores, boxes_lidar=boxes)
+            if with_labels:
+                anno["pred_labels"] = labels
+        anno["frame_id"] = batch_dict["frame_id"][index]
+        anno["metadata"] = batch_dict["metadata"][index]
+        annos.append(anno)
+    return annos
+
+
+def lidar_kitti_eval(det_annos, gt_annos, map_name_to_kitti, kitti_class_names, info_with_fakelidar=False):
+    """The KITTI AP table of boxes in the LiDAR frame: `boxes_lidar` of the detections and `gt_boxes_lidar` of the ground truth
+    (paired by position, both changed in place) become camera location / dimensions / rotation_y / alpha with the placeholder
+    image box, so every object is Easy.  map_name_to_kitti names every class present; info_with_fakelidar applies to the
+    ground truth only."""
+    from .kitti import kitti_utils
+    from .kitti.kitti_object_eval_python import eval as kitti_eval
+    for annos, key in ((det_annos, "boxes_lidar"), (gt_annos, "gt_boxes_lidar")):
+        for anno in annos:
+            anno["name"] = np.array(anno["name"], dtype=object)
+            anno[key] = np.asarray(anno[key], np.float64)[:, :7]
+    kitti_utils.transform_annotations_to_kitti_format(det_annos, map_name_to_kitti=map_name_to_kitti)
+    kitti_utils.transform_annotations_to_kitti_format(gt_annos, map_name_to_kitti=map_name_to_kitti, info_with_fakelidar=info_with_fakelidar)
+    return kitti_eval.get_official_eval_result(gt_annos, det_annos, kitti_class_names)
+
+
 class DatasetTemplate(torch_data.Dataset):
     def __init__(self, dataset_cfg=None, class_names=None, training=True, root_path=None, logger=None):
         super().__init__()
@@ -49,6 +90,16 @@ class DatasetTemplate(torch_data.Dataset):
         self._merge_all_iters_to_one_epoch = merge
         if merge:
             self.total_epochs = epochs
+
+    def _log(self, text):
+        if self.logger is not None:
+            self.logger.info(text)
+
+    def __len__(self):
+        """The datasets that keep their frames in `self.infos`; the others define their own."""
+        if self._merge_all_iters_to_one_epoch:
+            return len(self.infos) * self.total_epochs
+        return len(self.infos)
 
     def prepare_data(self, data_dict):
         """gt filtering by class -> class-id column -> feature encoding -> processor queue."""

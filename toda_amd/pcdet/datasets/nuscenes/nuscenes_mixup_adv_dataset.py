@@ -17,9 +17,9 @@ boxes' names too: gt_sampling pastes into either half).  The objects of the GT d
 SHIFT_COOR their stored centres are moved once, at construction: a pasted box and its points then land in the shifted scene
 (the reference pastes both at their unshifted height).
 
-MI355X layout: a frame is always a CUDA tensor, also with MAX_SWEEPS 1 (one upload, ops.sweeps_merge, one compaction).  The
-adversarial edit (reference get_ps_adv_lidar_with_sweeps, :191-274) is ops.adv_edit (csrc/adv_frame.hip): the host draws, per
-pseudo box above PSEUDO_THRESH and in box order, op = np.random.randint(3), frac = np.random.random() and a uint32 seed; the
+MI355X layout: a frame is always a CUDA tensor, also with MAX_SWEEPS 1 (SweepDataset.merge_info: one upload, one merge pass,
+one compaction).  The adversarial edit (reference get_ps_adv_lidar_with_sweeps, :191-274) is ops.adv_edit
+(csrc/adv_frame.hip): the host draws, per pseudo box above PSEUDO_THRESH and in box order, op = np.random.randint(3), frac = np.random.random() and a uint32 seed; the
 frame's voxel keys are sorted once and uploaded with the gradients; the device finds the rows of every box, draws the subsets
 and edits the cloud, which never returns to the host.  The reference's helper module (pcdet/utils/perturb_utils.py) is not
 part of its tree: the voxel lookup and the box test are this project's, as in SyntheticMixupPairDataset.
@@ -39,14 +39,13 @@ import pickle
 from pathlib import Path
 
 import numpy as np
-import torch
 
 from ..augmentor.database_sampler import DataBaseSampler
 # the pair policy and the edit are shared with KittiMixUpAdvDataset (mixup_dataset.MixUpAdvPairPolicy); the names below stay
 # importable from this module
 from ..mixup_dataset import (ADV_ADD, ADV_MODIFY, ADV_REMOVE, MIXUP_TYPES, MixUpAdvPairPolicy, _boxes7, draw_mixup_indices,  # noqa: F401
                              encode_frame, finish_half, fmix32, subset_keys, subset_size)
-from .nuscenes_dataset import EGO_RADIUS, NuScenesDataset
+from .nuscenes_dataset import NuScenesDataset
 
 
 class NuScenesMixUpAdvDataset(MixUpAdvPairPolicy, NuScenesDataset):
@@ -95,12 +94,7 @@ class NuScenesMixUpAdvDataset(MixUpAdvPairPolicy, NuScenesDataset):
 
     def frame_points(self, info):
         """[n, 5] CUDA tensor of one info: key frame and MAX_SWEEPS - 1 sweeps merged, SHIFT_COOR added."""
-        from .... import ops
-        paths, matrices, lags, drop_ego = self._sweep_table(info, self.max_sweeps)
-        rows, offsets = self.read_rows(paths)
-        shift = np.array(self.shift_coor, dtype=np.float32) if self.shift_coor else None
-        out, flags = ops.sweeps_merge(torch.from_numpy(rows).cuda(), offsets, matrices, lags, drop_ego, radius=EGO_RADIUS, shift=shift)
-        return ops.RowBuffer(out.shape[0], 5, out.device).append(out, flags, 1).finish()
+        return self.merge_info(info, self.max_sweeps, shift=np.array(self.shift_coor, dtype=np.float32) if self.shift_coor else None)
 
     # ---- frames and items
     def frame(self, k, adversarial, draws=None):

@@ -31,7 +31,7 @@ import numpy as np
 import torch
 
 from ...utils import box_utils, common_utils
-from ..dataset import DatasetTemplate
+from ..dataset import DatasetTemplate, lidar_kitti_eval, lidar_prediction_dicts
 
 MAP_NAME_TO_KITTI = {"Vehicle": "Car", "Pedestrian": "Pedestrian", "Cyclist": "Cyclist", "Sign": "Sign", "Car": "Car"}
 FRAME_COLS_MIN = 6               # x, y, z, intensity, elongation, NLZ flag
@@ -48,10 +48,6 @@ class WaymoDataset(DatasetTemplate):
         self.frame_path = self.root_path / other if other else self.data_path
         self.use_nlz = not dataset_cfg.get("DISABLE_NLZ_FLAG_ON_POINTS", False)
         self.set_split(dataset_cfg.DATA_SPLIT[self.mode])
-
-    def _log(self, text):
-        if self.logger is not None:
-            self.logger.info(text)
 
     # ---- reading
     def set_split(self, split):
@@ -126,11 +122,6 @@ class WaymoDataset(DatasetTemplate):
         return points_all
 
     # ---- samples
-    def __len__(self):
-        if self._merge_all_iters_to_one_epoch:
-            return len(self.infos) * self.total_epochs
-        return len(self.infos)
-
     def raw_frame(self, index, host=False):
         """Frame `index` before prepare_data: {points, frame_id, metadata} and, with annotations, gt_names / gt_boxes /
         num_points_in_gt without the `unknown` objects (and, in training with FILTER_EMPTY_BOXES_FOR_TRAIN, without the empty
@@ -168,19 +159,7 @@ class WaymoDataset(DatasetTemplate):
     def generate_prediction_dicts(batch_dict, pred_dicts, class_names, output_path=None):
         """Per frame {name, score, boxes_lidar, frame_id, metadata}; a frame without detections keeps the zero-length float
         fields of the reference's template."""
-        annos = []
-        for index, box_dict in enumerate(pred_dicts):
-            scores = box_dict["pred_scores"].detach().cpu().numpy()
-            boxes = box_dict["pred_boxes"].detach().cpu().numpy()
-            labels = box_dict["pred_labels"].detach().cpu().numpy()
-            n = scores.shape[0]
-            anno = {"name": np.zeros(n), "score": np.zeros(n), "boxes_lidar": np.zeros([n, 7])}
-            if n:
-                anno.update(name=np.array(class_names)[labels - 1], score=scores, boxes_lidar=boxes)
-            anno["frame_id"] = batch_dict["frame_id"][index]
-            anno["metadata"] = batch_dict["metadata"][index]
-            annos.append(anno)
-        return annos
+        return lidar_prediction_dicts(batch_dict, pred_dicts, class_names, with_labels=False)
 
     def evaluation(self, det_annos, class_names, **kwargs):
         if not self.infos or "annos" not in self.infos[0]:
@@ -199,18 +178,8 @@ class WaymoDataset(DatasetTemplate):
         """The KITTI AP table in the LiDAR frame: detections and infos pair up by position, Vehicle scores as Car, every object
         gets the placeholder image box (so all are Easy); INFO_WITH_FAKELIDAR applies to the ground truth only.  `unknown`
         objects, which have no KITTI name, are left out of the ground truth (a stock preparation stores none)."""
-        from ..kitti import kitti_utils
-        from ..kitti.kitti_object_eval_python import eval as kitti_eval
-        for anno in eval_det_annos + eval_gt_annos:
-            anno["name"] = np.array(anno["name"], dtype=object)
-        for anno in eval_det_annos:
-            anno["boxes_lidar"] = np.asarray(anno["boxes_lidar"], np.float64)[:, :7]
-        for anno in eval_gt_annos:
-            anno["gt_boxes_lidar"] = np.asarray(anno["gt_boxes_lidar"], np.float64)[:, :7]
-        kitti_utils.transform_annotations_to_kitti_format(eval_det_annos, map_name_to_kitti=MAP_NAME_TO_KITTI)
-        kitti_utils.transform_annotations_to_kitti_format(eval_gt_annos, map_name_to_kitti=MAP_NAME_TO_KITTI,
-                                                          info_with_fakelidar=self.dataset_cfg.get("INFO_WITH_FAKELIDAR", False))
-        return kitti_eval.get_official_eval_result(eval_gt_annos, eval_det_annos, [MAP_NAME_TO_KITTI[c] for c in class_names])
+        return lidar_kitti_eval(eval_det_annos, eval_gt_annos, MAP_NAME_TO_KITTI, [MAP_NAME_TO_KITTI[c] for c in class_names],
+                                info_with_fakelidar=self.dataset_cfg.get("INFO_WITH_FAKELIDAR", False))
 
     def aph_eval(self, det_annos, class_names, route="device"):
         """LEVEL_1 / LEVEL_2 AP and APH per object type (waymo_eval.py, DESIGN.md 3.15): detections and infos pair up by position;
