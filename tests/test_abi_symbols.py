@@ -1,6 +1,9 @@
 """The C-ABI library loads on a GPU-less host and exports every symbol include/toda.h declares."""
+import ctypes as C
 import os
 import re
+
+import pytest
 
 from toda_amd import lib as L
 
@@ -22,6 +25,82 @@ def test_header_symbols_all_exported_and_bound():
         assert s in L.SIGNATURES, f"{s} has no ctypes prototype in toda_amd/lib.py"
     assert sorted(L.SIGNATURES) == syms
     assert lib.toda_abi_version() == 3
+
+
+_vp, _i, _sz, _dbl, _f, _u, _ll = C.c_void_p, C.c_int, C.c_size_t, C.c_double, C.c_float, C.c_uint, C.c_longlong
+
+# written out by hand: one entry point per kind of declaration the header uses
+EXPECTED = {
+    "toda_last_error": (C.c_char_p, []),
+    "toda_gridindex_bytes": (_sz, [_i, _vp]),
+    "toda_bn2d_fwd": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _u, _vp]),
+    "toda_conv3x3_narrow_fwd": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _ll, _vp, _vp]),
+    "toda_points_sector": (_i, [_vp, _i, _vp, _i, _dbl, _dbl, _vp, _vp]),
+    "toda_clip_adam_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _f, _f, _f, _f, _f, _i, _vp]),
+    "toda_conv3x3_transform_weight_batch": (_i, [_vp, _i, _vp]),
+    "toda_anchor_assign": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "toda_anchor_assign_workspace_bytes": (_sz, [_i, _i]),
+}
+
+
+@pytest.mark.parametrize("name", sorted(EXPECTED))
+def test_prototypes_read_from_the_header(name):
+    assert L.SIGNATURES[name] == EXPECTED[name]
+    assert len(L.ARG_NAMES[name]) == len(EXPECTED[name][1])
+
+
+def test_argument_names_and_limits_read_from_the_header():
+    assert L.ARG_NAMES["toda_last_error"] == ()
+    assert L.ARG_NAMES["toda_gridindex_bytes"] == ("batch", "shape_host")
+    assert L.ARG_NAMES["toda_points_sector"] == ("points", "n", "n_dev", "c", "lo", "hi", "flags", "stream")
+    assert set(L.ARG_NAMES) == set(L.SIGNATURES)
+    limits = {"TODA_NUSC_MAX_PRED": 500, "TODA_NUSC_MAX_GT": 2048, "TODA_WAYMO_MAX_PRED": 512, "TODA_WAYMO_MAX_GT": 512,
+              "TODA_WAYMO_CUTOFFS": 101, "TODA_LYFT_MAX_CUTOFFS": 16, "TODA_OK": 0, "TODA_EINVAL": -1, "TODA_FAULT_FPS": 4}
+    assert {k: L.DEFINES[k] for k in limits} == limits
+    assert "TODA_H_" not in L.DEFINES
+    from toda_amd import ops
+    assert (ops.NUSC_MAX_PRED, ops.NUSC_MAX_GT, ops.WAYMO_MAX_PRED, ops.WAYMO_MAX_GT, ops.WAYMO_CUTOFFS, ops.LYFT_MAX_CUTOFFS) == (500, 2048, 512, 512, 101, 16)
+
+
+SYNTHETIC = """
+/* toda_in_a_comment(int a); */
+#ifndef X_H_
+#define TODA_LIMIT 12   /* a limit */
+#define TODA_NEGATIVE (-3)
+#define TODA_BIT 4u
+#define TODA_NOT_A_NUMBER (TODA_LIMIT + 1)
+extern "C" {
+typedef struct toda_entry { const float* w; int n; } toda_entry;
+const char* toda_name(void);   // toda_in_a_line_comment(int a);
+size_t toda_bytes(int batch, const int32_t* shape_host /*[3] D H W*/);
+int toda_many(const float* const* rows_host, unsigned long long* cells, const toda_entry* entries,
+              const int32_t shape[3], unsigned epoch, long long total,
+              float eps, double lo, size_t ws_bytes, void* stream);
+}
+"""
+
+
+def test_parser_on_a_synthetic_header():
+    sig, names, defines = L.parse_header(SYNTHETIC)
+    assert sig == {"toda_name": (C.c_char_p, []), "toda_bytes": (_sz, [_i, _vp]),
+                   "toda_many": (_i, [_vp, _vp, _vp, _vp, _u, _ll, _f, _dbl, _sz, _vp])}
+    assert names == {"toda_name": (), "toda_bytes": ("batch", "shape_host"),
+                     "toda_many": ("rows_host", "cells", "entries", "shape", "epoch", "total", "eps", "lo", "ws_bytes", "stream")}
+    assert defines == {"TODA_LIMIT": 12, "TODA_NEGATIVE": -3, "TODA_BIT": 4}
+
+
+@pytest.mark.parametrize("decl, named", [
+    ("int toda_short(short n);", "toda_short"),                          # a scalar type with no mapping
+    ("int toda_wide(int n, int64_t total);", "toda_wide"),
+    ("int32_t toda_ret(int n);", "toda_ret"),
+    ("int toda_unnamed(int, int n);", "toda_unnamed"),
+    ("int toda_callback(void (*done)(int), int n);", "toda_callback"),   # declarations the pattern does not cover
+    ("TODA_API(int) toda_wrapped(int n);", "toda_wrapped"),
+    ("int toda_twice(int n); int toda_twice(int n);", "3 times .* 2 prototypes"),      # counted with toda_fine
+])
+def test_parser_raises_on_what_it_does_not_understand(decl, named):
+    with pytest.raises(RuntimeError, match=named):
+        L.parse_header("int toda_fine(int n);\n" + decl)
 
 
 def test_host_side_size_queries_need_no_gpu():

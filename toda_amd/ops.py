@@ -1929,7 +1929,7 @@ def eval_match(overlaps, ov_off, det_off, gt_off, ign_det, ign_gt, score, det_al
 
 NUSC_CLASSES = ("car", "truck", "bus", "trailer", "construction_vehicle", "pedestrian", "motorcycle", "bicycle", "traffic_cone", "barrier")
 NUSC_DIST_THS = (0.5, 1.0, 2.0, 4.0)
-NUSC_MAX_PRED, NUSC_MAX_GT = 500, 2048                  # TODA_NUSC_MAX_PRED / TODA_NUSC_MAX_GT of include/toda.h
+NUSC_MAX_PRED, NUSC_MAX_GT = L.DEFINES["TODA_NUSC_MAX_PRED"], L.DEFINES["TODA_NUSC_MAX_GT"]
 
 
 def nusc_eval_prepare(rows, sample, cls, G, ego):
@@ -1975,7 +1975,7 @@ def nusc_eval_match(pred, score, pred_attr, gt, gt_attr, pred_off, gt_off, seg_c
     return match, err
 
 
-WAYMO_MAX_PRED, WAYMO_MAX_GT, WAYMO_CUTOFFS = 512, 512, 101      # TODA_WAYMO_* of include/toda.h
+WAYMO_MAX_PRED, WAYMO_MAX_GT, WAYMO_CUTOFFS = L.DEFINES["TODA_WAYMO_MAX_PRED"], L.DEFINES["TODA_WAYMO_MAX_GT"], L.DEFINES["TODA_WAYMO_CUTOFFS"]
 WAYMO_TYPES = ("Vehicle", "Pedestrian", "Sign", "Cyclist")       # estimator types 1..4
 
 
@@ -2038,7 +2038,7 @@ def waymo_eval_match(iou, score, pred_heading, gt_heading, gt_level, pred_off, g
     return tp, fn, fp, sum_ha, match
 
 
-LYFT_MAX_CUTOFFS = 16                                            # TODA_LYFT_MAX_CUTOFFS of include/toda.h
+LYFT_MAX_CUTOFFS = L.DEFINES["TODA_LYFT_MAX_CUTOFFS"]
 LYFT_IOU_THRESHOLDS = (0.5, 0.55, 0.6, 0.65, 0.7, 0.75, 0.8, 0.85, 0.9, 0.95)
 
 

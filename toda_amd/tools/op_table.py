@@ -59,10 +59,15 @@ class OpTable:
         def timed(*a):
             if not self.enabled:
                 return fn(*a)
-            key, cost = getattr(self, "_c_" + name)(a)
+            key, cost = self.cost_of(name, a)
             return self._bracket((name,) + key, cost, fn, *a)
 
         setattr(self.lib, name, timed)
+
+    @classmethod
+    def cost_of(cls, name, args):
+        """(key, cost) of one call of a C entry point: its cost function gets the arguments under the parameter names of include/toda.h."""
+        return getattr(cls, "_c_" + name)(dict(zip(L.ARG_NAMES[name], args)))
 
     def _wrap_py(self, name, cost_fn):
         fn = getattr(ops, name)
@@ -121,10 +126,10 @@ class OpTable:
         return (b, cin, cout, h, w), ("fixed", 4.0 * b * h * w * (cin + cout) + 4.0 * 9 * cin * cout, 2.0 * 9 * cin * cout * b * h * w,
                                       "direct-convolution FLOPs (Winograd-domain contraction: 1/4 of them)")
 
-    # C entry points: argument tuples as toda_amd/lib.py SIGNATURES
+    # C entry points: a = the call's arguments by the parameter names of include/toda.h
     @staticmethod
     def _c_toda_voxelize_hard(a):
-        n, c, max_pts, cap = a[1], a[2], a[6], a[7]
+        n, c, max_pts, cap = a["n"], a["c"], a["max_pts"], a["max_voxels"]
         m = min(cap, n)
         return (n, c, max_pts), ("fixed", 4.0 * n * c + 2 * 4.0 * m * max_pts * c + 20.0 * m, 0.0, "M bounded by min(cap, points)")
 
@@ -136,134 +141,136 @@ class OpTable:
 
     @classmethod
     def _c_toda_voxelize_batch(cls, a):
-        batch, c, max_pts, cap = a[2], a[4], a[9], a[10]
-        ns = cls._host_i32(a[1], batch)
+        batch, c, max_pts, cap = a["batch"], a["c"], a["max_pts"], a["max_voxels"]
+        ns = cls._host_i32(a["n_points_host"], batch)
         byts = sum(4.0 * n * c + 2 * 4.0 * min(cap, n) * max_pts * c + 20.0 * min(cap, n) for n in ns)
         return (batch, sum(ns), c, max_pts), ("fixed", byts, 0.0, "whole batch (3 launches): per sample 4NC + 8MPC + 20M, M bounded by min(cap, points)")
 
-    def _c_toda_gridindex_from_coords_unordered(self, a):
-        n = a[1]
+    @staticmethod
+    def _c_toda_gridindex_from_coords_unordered(a):
+        n = a["n"]
         return (n,), ("fixed", 16.0 * n + 8.0 * n, 0.0, "16 B coordinate row + one 8-byte cell per site; n = upper bound (cap) of the rows")
 
     _c_toda_gridindex_clear = _c_toda_gridindex_from_coords_unordered
 
     @classmethod
     def _c_toda_gridindex_from_bitmap(cls, a):
-        batch = a[1]
-        di, do = cls._host_i32(a[2], 3), cls._host_i32(a[6], 3)      # (a[11]: the input rows are marked)
+        batch = a["batch"]
+        di, do = cls._host_i32(a["shape_in_host"], 3), cls._host_i32(a["shape_out_host"], 3)
         ci, co = batch * di[0] * di[1] * di[2] / 32.0, batch * do[0] * do[1] * do[2] / 32.0
         return (batch, *do), ("fixed", 8.0 * ci + 8.0 * co, 0.0, "one pass over the input bitmap's and the output bitmap's 8-byte words (output rows not counted)")
 
     @staticmethod
     def _c_toda_rulebook_class_order(a):
-        n = a[1]
+        n = a["n_in"]
         return (n,), ("fixed", 16.0 * n + 5.0 * n, 0.0, "16 B coordinate row in, order + class out")
 
     @staticmethod
     def _c_toda_mean_vfe_fwd(a):
-        m, p, c = a[2], a[3], a[4]
+        m, p, c = a["m"], a["p"], a["c"]
         return (m, p, c), ("fixed", 4.0 * m * (p * c + c + 1), 0.0, "")
 
     _c_toda_mean_vfe_bwd = _c_toda_mean_vfe_fwd
 
-    def _c_toda_gridindex_from_coords(self, a):
-        n = a[1]
+    @staticmethod
+    def _c_toda_gridindex_from_coords(a):
+        n = a["n"]
         return (n,), ("fixed", 16.0 * n + 8.0 * n, 0.0, "16 B coordinate row + one 8-byte cell per site (bitmap clear / scan not counted)")
 
     @staticmethod
     def _c_toda_gridindex_from_conv(a):
-        n = a[1]
+        n = a["n_in"]
         return (n,), ("fixed", 16.0 * n + 16.0 * n, 0.0, "16 B in + 16 B out per site (upper bound on N_out = N_in)")
 
     @staticmethod
     def _c_toda_rulebook_subm(a):
-        n = a[1]
+        n = a["n"]
         return (n,), ("fixed", 16.0 * n + 16.0 * n + 4.0 * 27 * n, 0.0, "16 N_in + 16 N_out + the 27 x N table it writes")
 
     @staticmethod
     def _c_toda_rulebook_conv(a):
-        n_in, n_out = a[1], a[9]
+        n_in, n_out = a["n_in"], a["n_out"]
         return (n_in, n_out), ("fixed", 16.0 * n_in + 16.0 * n_out + 4.0 * 27 * (n_in + n_out), 0.0, "both tables (o2i, i2o)")
 
-    @staticmethod
-    def _c_toda_sparse_to_dense_fwd(a):
-        import ctypes
-        n, c, batch = a[2], a[3], a[4]
-        addr = a[5].value if hasattr(a[5], "value") else int(a[5])
-        d, h, w = ctypes.cast(addr, ctypes.POINTER(ctypes.c_int32))[0:3]
+    @classmethod
+    def _c_toda_sparse_to_dense_fwd(cls, a):
+        n, c, batch = a["n"], a["c"], a["batch"]
+        d, h, w = cls._host_i32(a["shape_host"], 3)
         return (n, c, batch, d, h, w), ("fixed", 4.0 * n * c + 4.0 * batch * c * d * h * w, 0.0, "sparse rows + the dense map")
 
     _c_toda_sparse_to_dense_bwd = _c_toda_sparse_to_dense_fwd
 
     @staticmethod
     def _c_toda_rows_moments(a):
-        n, c = a[1], a[2]
+        n, c = a["n"], a["c"]
         return (n, c), ("fixed", 4.0 * n * c, 0.0, "")
 
     @staticmethod
     def _c_toda_rows_affine_act(a):
-        n, c = a[4], a[5]
-        return (n, c), ("fixed", (12.0 if a[3] else 8.0) * n * c, 0.0, "")
+        n, c = a["n"], a["c"]
+        return (n, c), ("fixed", (12.0 if a["residual"] else 8.0) * n * c, 0.0, "")
 
     @staticmethod
     def _c_toda_rows_bn_bwd_res(a):
-        n, c = a[5], a[6]
+        n, c = a["n"], a["c"]
         return (n, c), ("fixed", 20.0 * n * c, 0.0, "")
 
     @staticmethod
     def _c_toda_bn2d_fwd(a):
-        b, c, hw = a[1], a[2], a[3]
+        b, c, hw = a["batch"], a["c"], a["hw"]
         return (b, c, hw), ("fixed", 8.0 * b * c * hw, 0.0, "x read once, y written once")
 
     @staticmethod
     def _c_toda_bn2d_bwd(a):
-        b, c, hw = a[2], a[3], a[4]
+        b, c, hw = a["batch"], a["c"], a["hw"]
         return (b, c, hw), ("fixed", 12.0 * b * c * hw, 0.0, "x once, dy once, dx once")
 
     @staticmethod
     def _c_toda_bn2d_fwd_into(a):
-        b, c, hw = a[1], a[2], a[3]
-        return (b, c, hw, a[12]), ("fixed", 8.0 * b * c * hw, 0.0, "x read once, y written once into its channel slice of the concatenated map")
+        b, c, hw = a["batch"], a["c"], a["hw"]
+        return (b, c, hw, a["y_channels"]), ("fixed", 8.0 * b * c * hw, 0.0, "x read once, y written once into its channel slice of the concatenated map")
 
     @staticmethod
     def _c_toda_bn2d_bwd_from(a):
-        b, c, hw = a[4], a[5], a[6]
-        return (b, c, hw, a[2]), ("fixed", 12.0 * b * c * hw, 0.0, "x once, dy (a channel slice) once, dx once")
+        b, c, hw = a["batch"], a["c"], a["hw"]
+        return (b, c, hw, a["dy_channels"]), ("fixed", 12.0 * b * c * hw, 0.0, "x once, dy (a channel slice) once, dx once")
 
     @staticmethod
     def _c_toda_clip_adam_step(a):
-        n_chunks = a[7]
+        n_chunks = a["n_chunks"]
         p = 8192.0 * n_chunks
         return (n_chunks,), ("fixed", 4.0 * 9 * p, 0.0, "g twice, p / m / v read and written, g written: 36 bytes per parameter (upper bound: whole chunks)")
 
     @staticmethod
     def _pix_gemm(a, s, what):
-        b, cin, cout, h, w = a[2], a[3], a[4], a[5], a[6]
+        b, cin, cout, h, w = a["batch"], a["cin"], a["cout"], a["H"], a["W"]
         if what == "conv":       # 3x3 / stride 2: out = (h/2, w/2), 9 taps
             flops, byts = 2.0 * 9 * cin * cout * b * (h // 2) * (w // 2), 4.0 * b * (cin * h * w + cout * (h // 2) * (w // 2)) + 4.0 * 9 * cin * cout
         else:                    # transposed conv, kernel = stride s: out = (s h, s w)
             flops, byts = 2.0 * cin * cout * s * s * b * h * w, 4.0 * b * h * w * (cin + cout * s * s) + 4.0 * cin * cout * s * s
         return (b, cin, cout, h, w, s), ("fixed", byts, flops, "")
 
-    def _c_toda_conv3x3s2_fwd(self, a):
-        return self._pix_gemm(a, 2, "conv")
+    @classmethod
+    def _c_toda_conv3x3s2_fwd(cls, a):
+        return cls._pix_gemm(a, 2, "conv")
 
     _c_toda_conv3x3s2_dgrad = _c_toda_conv3x3s2_fwd
     _c_toda_conv3x3s2_wgrad = _c_toda_conv3x3s2_fwd
 
-    def _c_toda_deconv_fwd(self, a):
-        return self._pix_gemm(a, a[7], "deconv")
+    @classmethod
+    def _c_toda_deconv_fwd(cls, a):
+        return cls._pix_gemm(a, a["s"], "deconv")
 
     _c_toda_deconv_dgrad = _c_toda_deconv_fwd
     _c_toda_deconv_wgrad = _c_toda_deconv_fwd
 
     @staticmethod
     def _c_toda_spconv_pack_weight(a):
-        return (a[1], a[2], a[3]), ("fixed", 8.0 * a[1] * a[2] * a[3], 0.0, "")
+        return (a["cout"], a["k_vol"], a["cin"]), ("fixed", 8.0 * a["cout"] * a["k_vol"] * a["cin"], 0.0, "")
 
     @staticmethod
     def _c_toda_conv3x3_transform_weight(a):
-        return (a[1], a[2], a[3]), ("fixed", 4.0 * a[1] * a[2] * (9 + 36 * (2 if a[3] == 2 else 1)), 0.0, "")
+        return (a["cout"], a["cin"], a["mode"]), ("fixed", 4.0 * a["cout"] * a["cin"] * (9 + 36 * (2 if a["mode"] == 2 else 1)), 0.0, "")
 
     @staticmethod
     def _c_toda_center_assign(a):
